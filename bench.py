@@ -15,9 +15,20 @@ The step calls the operator API the reference exposes - 32 pre-built PyramidKVCl
 Multi-GPU (N > 1): the headline IS BASELINE config 4 - ONE [1,32,32768,128] sequence, head-sharded: rank r owns 32/N query
 heads and their 8/N un-expanded KV heads (one KV head per GPU at N = 8), one RCCL all-gather of the selected indices
 (pyramidkv_amd/dist.py); "scaling": "strong".  The embarrassingly parallel weak leg (B = N sequences, H/N heads of each
-per GPU) is reported under `scaling_legs`, next to the all-gather's own latency.
+per GPU) is reported under `scaling_legs` (--full), next to the all-gather's own latency.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the contract fields (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...) and nothing it would have to run more work for.
+`--dump-outputs DIR` then also writes what the last timed step returned to its caller (rank 0's share), as float arrays:
+  DIR/indices.npy       [B, H, sum of the 32 layer budgets] every layer's selected token indices, layer after layer
+                        (beyond a quarter of the size bound: a fixed seeded sample, flat positions in indices_elements.npy),
+  DIR/k_compressed.npy  every layer's compacted K ([B, H, k + window, D] each), concatenated along the token axis,
+  DIR/v_compressed.npy  the same for V, and where it would exceed the size bound, a fixed seeded sample of the
+  DIR/kv_rows.npy       rows of both (flat row index b * H * T + h * T + t of the concatenated [B, H, T, D]),
+  DIR/exchanged_indices.npy  (under torch.distributed.run) the last layer's all-gathered indices.
+The inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+`--full` adds everything else, each part measured after the headline; rank 0's line then also carries
   `roofline`          dominant kernel (the K scan) of the headline workload,
   `roofline_kernels`  every kernel of the headline workload AND the north-star kernel at its target configuration:
                       `gather_cap2048_B1` / `gather_cap2048_B8` (SnapKV budget 2048, S = 32768; 67.1 MB x B),
@@ -49,11 +60,15 @@ NUM_LAYERS = 32
 D, W, E = 128, 8, 2
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check, per-kernel rooflines, extras, sweeps and CPU baselines (--no-cpu-baseline, --no-parity, --no-extras, --only-gqa-extra trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float, at most 64 MB in all)")
     ap.add_argument("--seq", type=int, default=32768)
     ap.add_argument("--budget", type=int, default=128)
     ap.add_argument("--heads", type=int, default=32)
@@ -69,7 +84,10 @@ def parse():
     ap.add_argument("--only-gqa-extra", action="store_true", help="of the extras run only the un-expanded-GQA leg (A/B sessions)")
     ap.add_argument("--cpu-layers", type=int, default=32, help="layer-calls per CPU-baseline pass (32 = the whole step)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work spent on the cpu_baseline sample")
-    return ap.parse_args()
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def layer_budgets(P, policy, cap, w, S):
@@ -111,6 +129,44 @@ def make_sets(B, Hl, S, dt, dev, seed, nsets, Hkv=None):
         sets.append(tuple(torch.randn(B, Hl if i == 0 or Hkv is None else Hkv, S, D, generator=gen, device=dev, dtype=torch.float32).to(dt)
                           for i in range(3)))
     return sets
+
+
+DUMP_BYTES = 60 * 10 ** 6         # --dump-outputs: all arrays together, leaving room for the .npy headers under 64 MB
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: the last timed step's outputs (module docstring) as DIR/<name>.npy.  Indices are written as float64
+    (exact), bf16 / fp16 K and V as float32 (exact).  K and V are written whole when they fit in what DUMP_BYTES leaves;
+    otherwise the same fixed, seeded sample of rows of both, sorted, with the flat row numbers in kv_rows.npy.  Indices
+    beyond a quarter of the bound (large batches and budgets) are sampled the same way (indices_elements.npy)."""
+    import numpy as np
+
+    def sample(n, fit):
+        return torch.randperm(n, generator=torch.Generator().manual_seed(0))[:fit].sort().values
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"indices": torch.cat(last["indices"], -1).double()}
+    fit = DUMP_BYTES // 4 // 16
+    if arrays["indices"].numel() > fit:
+        sel = sample(arrays["indices"].numel(), fit)
+        arrays["indices"] = arrays["indices"].reshape(-1)[sel.to(arrays["indices"].device)]
+        arrays["indices_elements"] = sel.double()
+    if last["exchanged"] is not None:
+        x = last["exchanged"].double()                       # [B, H, k] of the last layer: small; bounded all the same
+        arrays["exchanged_indices"] = x if x.numel() <= DUMP_BYTES // 128 else x.reshape(-1)[:DUMP_BYTES // 128]
+    kc = torch.cat([kv[0] for kv in last["kv"]], 2)
+    vc = torch.cat([kv[1] for kv in last["kv"]], 2)
+    left = DUMP_BYTES - sum(t.numel() * 8 for t in arrays.values())
+    rows = kc.numel() // kc.shape[-1]
+    fit = max(1, left // (2 * kc.shape[-1] * 4 + 8))        # a sampled row: its K and V in float32 + its row number
+    if rows > fit:
+        sel = sample(rows, fit)
+        arrays["kv_rows"] = sel.double()
+        sel = sel.to(kc.device)
+        kc, vc = kc.reshape(rows, -1)[sel], vc.reshape(rows, -1)[sel]
+    arrays["k_compressed"], arrays["v_compressed"] = kc.float(), vc.float()
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def make_clusters(P, policy, cap):
@@ -193,19 +249,24 @@ def main():
     clusters = make_clusters(P, a.policy, cap)
     host_issue = [0.0]
 
-    def timed_leg(B, steps, warmup, sets):
+    def timed_leg(B, steps, warmup, sets, dump=False):
         xch = pdist.PrefillIndexExchange(ks, B, Hl, dev, force=collective) if (collective and a.allgather == "prefill") else None
         # every layer's update_kv also leaves its selected indices in a buffer: the exchange's slot, or a plain tensor
         slots = [xch.slot(layer) if xch is not None else torch.empty(B, Hl, ks[layer], dtype=torch.int32, device=dev)
                  for layer in range(NUM_LAYERS)]
         g = sets[0][0].shape[1] // sets[0][1].shape[1]         # query heads per KV head handed over (1 = expanded K/V)
 
-        def one_step(keep=None):
+        def one_step(keep=None, collect=None):
             # The one exchange step of the path: the selected indices (KBs).  No layer's update_kv depends on another layer's
             # gathered indices, so (default) all 32 layers write into one buffer that is all-gathered ONCE per prefill;
             # "--allgather layer" issues one asynchronous collective per layer instead (at most two in flight).
             # keep = {layer: None}: the parity leg asks for these layers' (K_c, V_c, local indices) of THIS step function.
+            # collect = {} (--dump-outputs): every layer's (K_c, V_c) of this step and the exchanged indices; the previous
+            # step's are dropped first, so that every step reuses the same allocations.
             outs, pending = None, []
+            if collect is not None:
+                collect.clear()
+                collect["kv"] = []
             for layer in range(NUM_LAYERS):
                 q, k, v = sets[layer % len(sets)]
                 cl = clusters[layer]
@@ -214,6 +275,8 @@ def main():
                 idx = slots[layer]
                 if keep is not None and layer in keep:
                     keep[layer] = (kc, vc, idx.clone())
+                if collect is not None:
+                    collect["kv"].append((kc, vc))
                 if xch is None:
                     if collective:
                         pending.append(pdist.allgather_indices_async(idx, force=True))
@@ -224,20 +287,30 @@ def main():
                 outs = (outs[0], outs[1], xch.views(xch.gather_async())[-1])
             for h in pending:
                 outs = (outs[0], outs[1], h.wait())
+            if collect is not None:
+                collect["exchanged"] = outs[2] if collective else None
             return outs
 
+        collect = {} if dump else None
         for _ in range(warmup):
-            one_step()
+            one_step(collect=collect)
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            one_step()
+            one_step(collect=collect)
         barrier()
         el = time.perf_counter() - t0
+        last = None
+        if dump:                             # the last timed step's outputs, before anything else runs the step again
+            last = {"kv": collect["kv"], "indices": [s.clone() for s in slots],
+                    "exchanged": collect["exchanged"].clone() if collect["exchanged"] is not None else None}
         if dist is not None and world > 1:
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
+        ag_us = None
+        if not a.full:
+            return el, one_step, ag_us, last
         # this rank's host time to ISSUE one step (32 calls) into an empty queue - measured on its own: inside the timed loop the
         # host runs ahead of the device until the hardware queue is full and then waits for it
         barrier()
@@ -245,7 +318,6 @@ def main():
         one_step()
         host_issue[0] = time.perf_counter() - h0
         barrier()
-        ag_us = None
         if xch is not None:                  # the collective alone: issue + wait, nothing else on the device
             barrier()
             t0 = time.perf_counter()
@@ -253,7 +325,7 @@ def main():
                 xch.views(xch.gather_async())
             torch.cuda.synchronize()
             ag_us = (time.perf_counter() - t0) / 20 * 1e6
-        return el, one_step, ag_us
+        return el, one_step, ag_us, last
 
     # ---- headline leg ----
     # N = 1: one [B,H,S,D] sequence batch with K/V as the reference's update_kv receives them (after repeat_kv).
@@ -265,10 +337,36 @@ def main():
     if strong and a.kv_heads % world == 0 and (H // a.kv_heads) * W <= 256:
         Hkv = a.kv_heads // world
     sets = make_sets(B, Hl, S, dt, dev, 1234 + rank, NSETS, Hkv)
-    el, one_step, ag_us = timed_leg(B, a.steps, a.warmup, sets)
+    el, one_step, ag_us, last = timed_leg(B, a.steps, a.warmup, sets, dump=bool(a.dump_outputs))
     host_us_per_call = host_issue[0] / NUM_LAYERS * 1e6
     ms_per_step = el / a.steps * 1e3
     tokens_per_s = B * S * a.steps / el
+    if last is not None and rank == 0:
+        dump_outputs(a.dump_outputs, last)
+    del last
+    headline = {
+        "metric": "prefill tokens/s through KV-compress (PyramidKV budget=%d, S=%d, Llama-3-8B shapes)" % (cap, S),
+        "value": round(tokens_per_s, 1), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 4), "kv_compress_ms_per_layer": round(ms_per_step / NUM_LAYERS, 5),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": a.dtype,
+        "data": "synthetic",
+        "config": {"workload": "%s budget=%d window=8 maxpool7, 32 update_kv calls/step, [B=%d,H=%d,S=%d,D=128] %s"
+                               % (a.policy, cap, B, H, S, a.dtype),
+                   "global_batch": B, "seq_len": S, "heads_per_gpu": Hl,
+                   "kv_heads_per_gpu": Hkv if Hkv else Hl,
+                   "kv_layout": ("un-expanded GQA: %d of the model's %d KV heads per GPU, kv_group %d" % (Hkv, a.kv_heads, Hl // Hkv)) if Hkv
+                                else "expanded (after repeat_kv, as the reference's update_kv receives it)",
+                   "timed_through": "PyramidKVCluster.update_kv" if a.policy == "pyramidkv" else "SnapKVCluster.update_kv",
+                   "parallelism": ("head-shard x%d + 1 all-gather(indices) per %s" % (world, a.allgather)) if collective else "single GPU",
+                   "collective_backend": (backend if collective else None)},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(headline))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- parity of the TIMED path: the step function that was just timed, layers 0 and 31, against the CPU oracle ----
     parity = None
     if not a.no_parity:
@@ -344,21 +442,8 @@ def main():
                         v_["traffic_kernel_src_sha16"] = pmc.get("kernel_src_sha16")
                 break
 
-    out = {
-        "metric": "prefill tokens/s through KV-compress (PyramidKV budget=%d, S=%d, Llama-3-8B shapes)" % (cap, S),
-        "value": round(tokens_per_s, 1), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 4), "kv_compress_ms_per_layer": round(ms_per_step / NUM_LAYERS, 5),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": a.dtype,
-        "data": "synthetic",
-        "config": {"workload": "%s budget=%d window=8 maxpool7, 32 update_kv calls/step, [B=%d,H=%d,S=%d,D=128] %s"
-                               % (a.policy, cap, B, H, S, a.dtype),
-                   "global_batch": B, "seq_len": S, "heads_per_gpu": Hl,
-                   "kv_heads_per_gpu": Hkv if Hkv else Hl,
-                   "kv_layout": ("un-expanded GQA: %d of the model's %d KV heads per GPU, kv_group %d" % (Hkv, a.kv_heads, Hl // Hkv)) if Hkv
-                                else "expanded (after repeat_kv, as the reference's update_kv receives it)",
-                   "timed_through": "PyramidKVCluster.update_kv" if a.policy == "pyramidkv" else "SnapKVCluster.update_kv",
-                   "parallelism": ("head-shard x%d + 1 all-gather(indices) per %s" % (world, a.allgather)) if collective else "single GPU",
-                   "collective_backend": (backend if collective else None)},
+    out = dict(headline)
+    out.update({
         "roofline": kernels.get("logits"),
         "roofline_kernels": kernels,
         # one update_kv of this rank: host time to issue it (Python + the C call with its four launches) next to the device time
@@ -369,7 +454,7 @@ def main():
         "device_us_per_call": round(sum(r_["avg_us"] for r_ in kernels.values()), 2),
         "parity": parity,
         "kernel_src_sha16": src_id,
-    }
+    })
     if collective:
         out["config"]["process_group_backend"] = dist.get_backend()
         out["rccl_nranks"] = dist.get_world_size() if dist.get_backend() == "nccl" else None
@@ -384,7 +469,7 @@ def main():
     # ---- second multi-GPU leg: weak scaling (B = N sequences, H/N expanded heads of each per GPU: per-GPU bytes constant) ----
     if strong and not a.no_extras:
         wsets = make_sets(world, Hl, S, dt, dev, 99 + rank, 2)
-        wel, _, _ = timed_leg(world, a.steps, 1, wsets)
+        wel, _, _, _ = timed_leg(world, a.steps, 1, wsets)
         out["scaling_legs"] = {
             "strong_config4": {"global_batch": 1, "tokens_per_s": round(tokens_per_s, 1), "ms_per_step": round(ms_per_step, 4),
                                "kv_compress_ms_per_layer": round(ms_per_step / NUM_LAYERS, 5),

@@ -1,28 +1,24 @@
-"""The oracle against the REAL reference, live, on random configurations (CPU; only where /root/reference exists - this
-container; the GPU box has neither the reference nor this test's subject, so the module skips there).  The committed
-fixtures (tests/golden, test_oracle_golden.py) pin fixed cases; this walks seeded random ones through the same statement:
-oracle/pkv_oracle.py with the reference's own topk / sort calls == /root/reference/pyramidkv/pyramidkv_utils.py, bit for
-bit - K/V, the flat layout's metadata, pass-through identity, the LOOK-M merge."""
+"""The oracle against the REAL reference on random configurations (CPU).  The committed fixtures (tests/golden,
+test_oracle_golden.py) pin fixed cases; this walks seeded random ones through the same statement: oracle/pkv_oracle.py with
+the reference's own topk / sort calls == pyramidkv/pyramidkv_utils.py, bit for bit - K/V, the flat layout's metadata,
+pass-through identity, the LOOK-M merge.  What the reference returned on every one of these configurations is recorded in
+tests/golden/live_reference.json (bit digests of K / V, metadata, the exception it raised) and
+tests/golden/live_reference_indices.npz (the indices it selected), written by tests/golden/make_live_reference.py next to a
+checkout of the reference; the inputs are re-derived from their seeds and checked against the recorded checksums."""
 import contextlib
+import hashlib
 import io
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-REF_ROOT = "/root/reference"
-if not os.path.exists(os.path.join(REF_ROOT, "pyramidkv", "pyramidkv_utils.py")):
-    pytest.skip("the reference is not on this machine", allow_module_level=True)
-sys.path.insert(0, REF_ROOT)
-try:
-    from pyramidkv import pyramidkv_utils as ref            # the real reference
-except Exception as e:                                       # noqa: BLE001 - a missing optional dependency of the reference
-    pytest.skip("the reference does not import here: %r" % (e,), allow_module_level=True)
-
-from inputs import make_qkv, bits                            # noqa: E402
+from inputs import make_qkv, bits, checksum                  # noqa: E402
 from oracle import pkv_oracle as O                           # noqa: E402
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def quiet(fn, *a, **k):
@@ -53,30 +49,6 @@ def random_case(rng, policy):
     return c
 
 
-def run_reference(c, q, k, v):
-    w, cap, pol, mg = c["w"], c["cap"], c["policy"], c.get("merge")
-    if pol == "snapkv":
-        cl = ref.SnapKVCluster(window_size=w, max_capacity_prompt=cap, kernel_size=c["ks"], pooling=c["pool"], merge=mg)
-    elif pol == "pyramidkv":
-        cl = ref.PyramidKVCluster(num_hidden_layers=c["layers"], layer_idx=c["layer"], window_size=w, max_capacity_prompt=cap,
-                                  kernel_size=c["ks"], pooling=c["pool"], merge=mg)
-    elif pol == "h2o":
-        cl = ref.H2OKVCluster(window_size=w, max_capacity_prompt=cap, merge=mg)
-    elif pol == "streamingllm":
-        cl = ref.StreamingLLMKVCluster(window_size=w, max_capacity_prompt=cap, merge=mg)
-    elif pol == "adakv":
-        cl = ref.AdaKVCluster(window_size=w, kernel_size=c["ks"], pooling=c["pool"], max_capacity_prompt=cap, floor=c["floor"],
-                              normalize=c["normalize"], layer_idx=0, num_hidden_layers=32)
-    else:
-        cl = ref.HeadKVCluster(window_size=w, kernel_size=c["ks"], pooling=c["pool"], max_capacity_prompt=cap, layer_idx=0,
-                               num_hidden_layers=32, head_capacity=c["head_capacity"])
-    if pol in ("adakv", "headkv"):
-        kc, vc = quiet(cl.update_kv, k, q, v)
-        return kc, vc, cl
-    kc, vc = quiet(cl.update_kv, k, q, v, None, 1)
-    return kc, vc, cl
-
-
 def run_oracle(c, q, k, v):
     w, cap, pol, mg = c["w"], c["cap"], c["policy"], c.get("merge")
     if pol == "snapkv":
@@ -93,35 +65,76 @@ def run_oracle(c, q, k, v):
 
 
 POLICIES = ("snapkv", "pyramidkv", "h2o", "streamingllm", "adakv", "headkv")
+META_FIELDS = ("head_lens", "cu_klen", "cu_qlen", "cu_offset", "cu_head_offset")
+N_CASES, N_TIE_CASES = 40, 30
+
+
+def bits_digest(t):
+    """shape + dtype + sha256 of the bit pattern: equal digests <=> the same shape and the same bits."""
+    a = bits(t)
+    return "%s:%s:%s" % ("x".join(map(str, t.shape)), str(t.dtype).replace("torch.", ""), hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def configurations_case(policy):
+    """The seeded configurations of the equality test, in order."""
+    rng = np.random.default_rng(20260925 + POLICIES.index(policy))
+    return [random_case(rng, policy) for _ in range(N_CASES)]
+
+
+def configurations_tie(policy):
+    """The seeded configurations of the tie-rule test, in order (no merge: the selection is what is compared)."""
+    rng = np.random.default_rng(777 + POLICIES.index(policy))
+    out = []
+    for _ in range(N_TIE_CASES):
+        c = random_case(rng, policy)
+        c.pop("merge", None)
+        out.append(c)
+    return out
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    with open(os.path.join(GOLD, "live_reference.json")) as f:
+        rec = json.load(f)
+    with np.load(os.path.join(GOLD, "live_reference_indices.npz")) as z:
+        idx = {name: z[name] for name in z.files}
+    return rec, idx
+
+
+def _inputs(c, rec_case):
+    q, k, v = make_qkv(c["B"], c["H"], c["S"], 128, c["dtype"], c["kind"], c["seed"])
+    assert checksum(q, k, v) == rec_case["input_checksum"], ("inputs drifted from the recorded ones", c)
+    return q, k, v
 
 
 @pytest.mark.parametrize("policy", POLICIES)
-def test_oracle_equals_the_live_reference_on_random_configurations(policy):
-    rng = np.random.default_rng(20260925 + POLICIES.index(policy))
+def test_oracle_equals_the_live_reference_on_random_configurations(policy, recorded):
+    rec = recorded[0]["cases"][policy]
+    cases = configurations_case(policy)
+    assert len(rec) == len(cases)
     ran = compressed = 0
-    for _ in range(40):
-        c = random_case(rng, policy)
-        q, k, v = make_qkv(c["B"], c["H"], c["S"], 128, c["dtype"], c["kind"], c["seed"])
-        try:
-            kr, vr, cl = run_reference(c, q, k, v)
-        except Exception as e:                                # noqa: BLE001 - the oracle must refuse what the reference refuses
-            with pytest.raises(type(e)):
+    for c, r in zip(cases, rec):
+        assert r["config"] == c, "the recorded configurations are not this test's"
+        q, k, v = _inputs(c, r)
+        if "raises" in r:                                     # the oracle must refuse what the reference refuses
+            with pytest.raises(Exception) as ei:
                 run_oracle(c, q, k, v)
+            assert r["raises"] in [t.__name__ for t in type(ei.value).__mro__], (r["raises"], ei.value, c)
             continue
         out = run_oracle(c, q, k, v)
         ko, vo = out[0], out[1]
         ran += 1
-        if kr is k:                                           # pass-through returns the caller's objects (:219, :315)
+        if r["passthrough"]:                                  # pass-through returns the caller's objects (:219, :315)
             assert ko is k and vo is v, c
             continue
         compressed += 1
-        assert kr.shape == ko.shape and np.array_equal(bits(kr), bits(ko)), c
-        assert np.array_equal(bits(vr), bits(vo)), c
+        assert bits_digest(ko) == r["k"], c
+        assert bits_digest(vo) == r["v"], c
         if policy in ("adakv", "headkv"):
             meta = out[2]
-            for name in ("head_lens", "cu_klen", "cu_qlen", "cu_offset", "cu_head_offset"):
-                assert np.array_equal(getattr(meta, name).numpy(), getattr(cl, name).numpy()), (name, c)
-            assert meta.max_seqlen_k == int(cl.max_seqlen_k) and meta.klen_sum == int(cl.klen_sum), c
+            for name in META_FIELDS:
+                assert getattr(meta, name).numpy().tolist() == r["meta"][name], (name, c)
+            assert meta.max_seqlen_k == r["meta"]["max_seqlen_k"] and meta.klen_sum == r["meta"]["klen_sum"], c
     assert ran >= 30 and compressed >= 20, (ran, compressed)
 
 
@@ -142,23 +155,26 @@ def _recover_indices(K, Kc_past):
 
 
 @pytest.mark.parametrize("policy", ("snapkv", "pyramidkv", "h2o"))
-def test_canonical_tie_rule_selects_what_the_live_reference_selected(policy):
+def test_canonical_tie_rule_selects_what_the_live_reference_selected(policy, recorded):
     """What the HIP path implements is the oracle's CANONICAL tie rule (descending score, ascending index among equals); the
     reference's CPU topk orders equal scores its own way.  On random configurations the two select the same score-value
     sequence per head (O.equivalent_selection), and the same indices wherever the selected scores are distinct."""
-    rng = np.random.default_rng(777 + POLICIES.index(policy))
+    rec, rec_idx = recorded[0]["tie_cases"][policy], recorded[1]
+    cases = configurations_tie(policy)
+    assert len(rec) == len(cases)
     checked = identical_rows = 0
-    for _ in range(30):
-        c = random_case(rng, policy)
-        c.pop("merge", None)
-        q, k, v = make_qkv(c["B"], c["H"], c["S"], 128, c["dtype"], c["kind"], c["seed"])
-        kr, _, _ = run_reference(c, q, k, v)
-        if kr is k:
+    for j, (c, r) in enumerate(zip(cases, rec)):
+        assert r["config"] == c, "the recorded configurations are not this test's"
+        q, k, v = _inputs(c, r)
+        if r["passthrough"]:
+            continue
+        key = "%s_%02d" % (policy, j)
+        if key not in rec_idx:                                # duplicate source rows: the reference's choice is not recoverable
+            continue
+        ref_idx = torch.from_numpy(rec_idx[key].astype(np.int64))
+        if ref_idx.shape[2] == 0:
             continue
         w = c["w"]
-        ref_idx = _recover_indices(k[:, :, :-w], kr[:, :, :kr.shape[2] - w])
-        if ref_idx is None or ref_idx.shape[2] == 0:
-            continue
         if policy == "snapkv":
             out = O.snapkv_update_kv(k, q, v, w, c["cap"], c["ks"], c["pool"], topk_mode="canonical", return_indices=True)
         elif policy == "pyramidkv":

@@ -6,7 +6,7 @@ libs = [a for a in sys.argv[1:] if a.endswith(".so")]
 rounds = int(sys.argv[-1]) if sys.argv[-1].isdigit() else 3
 for r in range(rounds):
     for lib in libs:
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--only-gqa-extra", "--no-parity"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--only-gqa-extra", "--no-parity"],
                              env=dict(os.environ, PKV_LIB=os.path.abspath(lib)), capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if not line:

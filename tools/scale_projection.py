@@ -60,7 +60,7 @@ def allgather_nranks1():
     """bench.py as rank 0 of a 1-rank RCCL group: its `allgather_us`."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1",
                         "--no-cpu-baseline", "--no-extras", "--no-parity"], capture_output=True, text=True, env=env, timeout=600)
     for line in r.stdout.splitlines():
         if line.startswith("{"):
