@@ -29,6 +29,15 @@ constexpr int TK2_CMAX = 4096;           // candidates
 constexpr int TK2_NB = 2048;             // key buckets of the counting sort
 constexpr int TK2_BMAX = 512;            // a bucket may hold at most this many candidates: ranking inside a bucket is quadratic (round 6: a row
                                          // with ~1000 candidates on one fp16 subnormal value took 55 us here, 2x the full path it now takes)
+// routes of topk_kernel, as the debug build records them (word 14 of the trace buffer; tests/test_gpu_topk_routes.py decodes them)
+constexpr int TK_ROUTE_R1 = 0;           // one-level prefilter + bucket counting sort (algo 1)
+constexpr int TK_ROUTE_R2 = 1;           // zero-tied rows: positive keys ranked, then the lowest-index zeros
+constexpr int TK_ROUTE_R3 = 2;           // chunk-maxima prefilter, candidates ranked (rank_store)
+constexpr int TK_ROUTE_R4 = 3;           // chunk-maxima prefilter, two LSD radix passes over the candidates
+constexpr int TK_ROUTE_R5_RANK = 4;      // full radix select, ordered by rank counting
+constexpr int TK_ROUTE_R5_RADIX = 5;     // full radix select, ordered by two LSD radix passes
+constexpr int TK_ROUTE_R5_BITONIC = 6;   // full radix select, bitonic network
+constexpr int TK_GAVE_R1 = 0, TK_GAVE_R2 = 1, TK_GAVE_R34 = 2;
 
 // LDS layout: keys u16[16*Lw] | X u32[max(8192,kpad)] | hist u32[256] | misc u32[64] | X2 u32[8192] (if it fits)
 size_t topk_lds_bytes(int L, int k, int* Lw_out, int* kpad_out) {
@@ -172,6 +181,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
   const int niter = NI > 0 ? NI : Lw / 512;
 
 #define PKV_STAMP(i) do { if (PKV_TRACE(p) && tid == 0 && row == 0) PKV_TRACE(p)[i] = (unsigned long long)clock64(); } while (0)
+  // Route record (debug build): word 14 of the trace buffer collects, OR-ed over every launch on row 0 since the caller cleared it,
+  // bit r + v of the route that wrote the row (TK_ROUTE_*) and bit 32 + g + v of each route that was tried and gave up (TK_GAVE_*);
+  // v = 8 for the ADA instantiation, 16 for a segment of a long row.  The segments of row 0 record concurrently, hence the atomic.
+#define PKV_ROUTE_BITS(b) do { if (PKV_TRACE(p) && tid == 0 && row == 0)                                                      \
+    atomicOr(PKV_TRACE(p) + 14, (unsigned long long)(b) << ((ADA ? 8 : 0) + (p.nseg > 1 ? 16 : 0))); } while (0)
+#define PKV_ROUTE(r) PKV_ROUTE_BITS(1ull << (r))
+#define PKV_GAVE_UP(g) PKV_ROUTE_BITS(1ull << (32 + (g)))
   PKV_STAMP(0);
   const unsigned long long t_start = PKV_WGTRACE(p) ? wall_clock64() : 0ull;
   // ---- pass A: HBM/L2 -> ordered keys in LDS, histogram of the high byte.  All (<= 8) 16-B loads of a
@@ -444,6 +460,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
           if (rank < (uint32_t)k) emit((int)rank, mine);
         }
         PKV_STAMP(6);
+        PKV_ROUTE(TK_ROUTE_R1);
         if (PKV_WGTRACE(p) && tid == 0) { PKV_WGTRACE(p)[2 * (131072 + row)] = t_start; PKV_WGTRACE(p)[2 * (131072 + row) + 1] = wall_clock64(); }
         if (ADA) ada_epilogue();
         return;
@@ -589,10 +606,15 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
               }
               if (rank < (uint32_t)k) emit((int)rank, mine);
             }
-            // positions C .. k-1: the first k - C zeros in index order, one wave at a time
+            // positions C .. k-1: the first k - C zeros in index order, one wave at a time.  Every wave passes the same barriers:
+            // the ranking above ends at a different time in every wave (a crowded bucket keeps some waves there long after wave 0
+            // is done), so the read of miscu[6] is fenced off from wave w2's store to it by a barrier on each side - without the
+            // first one a late wave read wave 0's 0, left the loop a barrier early and, with ADA, paired its barriers with the
+            // wrong ones of the epilogue (waves summed the epilogue's `red` before the other waves had written it)
             const uint32_t need = C < (uint32_t)k ? (uint32_t)k - C : 0u;
             for (int w2 = 0; w2 < TK_WAVES; ++w2) {
-              const uint32_t rem = miscu[6];                       // workgroup-uniform
+              const uint32_t rem = miscu[6];                       // workgroup-uniform: nobody stores it between the barriers
+              __syncthreads();
               if (rem == 0u) break;
               if (wave == w2) {
                 uint32_t found = need - rem;
@@ -629,6 +651,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
             }
             if (miscu[6] == 0u) {
               PKV_STAMP(6);
+              PKV_ROUTE(TK_ROUTE_R2);
               if (PKV_WGTRACE(p) && tid == 0) { PKV_WGTRACE(p)[2 * (131072 + row)] = t_start; PKV_WGTRACE(p)[2 * (131072 + row) + 1] = wall_clock64(); }
               if (ADA) ada_epilogue();
               return;
@@ -638,6 +661,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
       }
     }
     // heavy ties: exact full path.  Its key table and counters start from scratch.
+    PKV_GAVE_UP(TK_GAVE_R1);
+    if (xstar <= order_key<T>((uint16_t)0)) PKV_GAVE_UP(TK_GAVE_R2);
     __syncthreads();
     transform_all();
     for (int i = tid; i < TK_CNT_WORDS; i += TK_THREADS) { X[i] = 0; X2[i] = 0; }
@@ -768,6 +793,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
       }
       if (C <= TK_FAST_C) {
         PKV_STAMP(5);
+        PKV_ROUTE(TK_ROUTE_R3);
         rank_store(cand, (int)C);
       } else {
         // 448 < C <= 4096 candidates, in index order: a STABLE sort by key alone is the canonical order, and
@@ -780,6 +806,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
         radix_pass(cand, tmp, table, hist, (int)C, ept, 0, tid);
         radix_pass(tmp, cand, table, hist, (int)C, ept, 1, tid);
         PKV_STAMP(5);
+        PKV_ROUTE(TK_ROUTE_R4);
         for (int i = tid; i < k; i += TK_THREADS) emit(i, cand[i]);
       }
       PKV_STAMP(6);
@@ -788,6 +815,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
       return;
     }
     // too many keys at or above x* (heavy ties): full path.  Its counters must start from zero.
+    PKV_GAVE_UP(TK_GAVE_R34);
     if (use_cmax) transform_all();       // the row is already in registers
     __syncthreads();
     for (int i = tid; i < TK_CNT_WORDS; i += TK_THREADS) { X[i] = 0; if (dual) X2[i] = 0; }
@@ -907,6 +935,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
 
   if (k <= TK_RANK_MAX) {
     // rank by counting: composites are unique, so ranks form a permutation of 0..k-1
+    PKV_ROUTE(TK_ROUTE_R5_RANK);
     if (tid < k) {
       const uint32_t mine = sel[tid];
       int rank = 0;
@@ -925,11 +954,13 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
     uint32_t* table = X2;                 // [16][256]
     uint32_t* sel2 = X2 + TK_WAVES * 256; // [4096]
     const int ept = (k + TK_THREADS - 1) / TK_THREADS;
+    PKV_ROUTE(TK_ROUTE_R5_RADIX);
     radix_pass(sel, sel2, table, hist, k, ept, 0, tid);
     radix_pass(sel2, sel, table, hist, k, ept, 1, tid);
     for (int i = tid; i < k; i += TK_THREADS) emit(i, sel[i]);
   } else {
     // bitonic network, descending (kpad is a power of two here)
+    PKV_ROUTE(TK_ROUTE_R5_BITONIC);
     int kp2 = 1;
     while (kp2 < k) kp2 <<= 1;
     for (int i = kpad + tid; i < kp2; i += TK_THREADS) sel[i] = 0;
@@ -952,6 +983,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkParams p) {
   if (PKV_WGTRACE(p) && tid == 0) { PKV_WGTRACE(p)[2 * (131072 + row)] = t_start; PKV_WGTRACE(p)[2 * (131072 + row) + 1] = wall_clock64(); }
   if (ADA) ada_epilogue();
 #undef PKV_STAMP
+#undef PKV_ROUTE_BITS
+#undef PKV_ROUTE
+#undef PKV_GAVE_UP
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -222,6 +222,11 @@ def test_topk_rows_that_are_mostly_zero(P, dt):
         s[:, torch.randperm(L, generator=g)[:30]] = 0.3
         _topk_check(P, s.to(tdt), 120)
         _topk_check(P, s.to(tdt), 400 if L >= 400 else L)
+    # negative scores that DO reach the zero branch (the rows above are decided by the ordinary attempt): 600 zeros in 600 chunks
+    # crowd zero's key bucket, so the ordinary attempt gives up and the zero walk finds its 90 zeros / all other scores tied at -0.5
+    # (every chunk passes the prefilter) and only 50 zeros, so the walk runs short and the full path decides
+    for s in _negative_zero_walk_rows():
+        _topk_check(P, s.to(tdt), 120)
     # crowded key buckets (round 6: ranking inside a bucket is quadratic; beyond 512 candidates in one bucket the small-k paths
     # hand the row to the full path): a plateau of 1500 equal scores across the k-th position, and positives on an 11-value grid
     L = 32760
@@ -242,6 +247,19 @@ def test_topk_rows_that_are_mostly_zero(P, dt):
     for kk in (17, 120, 234, 504):
         _, _, idx = P.ops.compress(q.to(DEV), k.to(DEV), v.to(DEV), 8, kk, "maxpool", 7, return_indices=True)
         assert torch.equal(idx.cpu().long(), O.topk_canonical(sc, kk)), kk
+
+
+def _negative_zero_walk_rows():
+    """Two [2, 32760] rows of negative scores, 30 positives and zeros: enough zeros for the zero walk / too few."""
+    g = torch.Generator().manual_seed(61)
+    out = []
+    for nzero in (600, 50):
+        s = -torch.rand(2, 32760, generator=g) if nzero == 600 else torch.full((2, 32760), -0.5)
+        ch = torch.randperm(4095, generator=g)[:nzero + 30] * 8 + 3
+        s[:, ch[:nzero]] = 0.0
+        s[:, ch[nzero:]] = 0.3
+        out.append(s)
+    return out
 
 
 def test_topk_small_and_strided(P):
