@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 201 /* 0.2.1: + pkv_runtime_reset, pkv_debug_scale_multiplier; pkv_ada_budget_rows validates its host
+#define PKV_VERSION 202 /* 0.2.2: + pkv_debug_score_route; no layout change.
+                           0.2.1: + pkv_runtime_reset, pkv_debug_scale_multiplier; pkv_ada_budget_rows validates its host
                            mirror (8-byte aligned uint64 [H], host_seq >= 0) like pkv_ada_select; no layout change.  0.2.0: pkv_desc starts with struct_size (the struct can grow without breaking hosts built against an
                            older header); pkv_ada_select's budget step is one launch; host mirrors are uint64 [H] of
                            self-validating words; fp32 at D = 256; 0.1.2: short Ada-SnapKV candidate lists */
@@ -291,6 +292,15 @@ PKV_API int pkv_prof_read(double* ms_sum, int64_t* launches, int reset); /* arra
 PKV_API int pkv_debug_build(void);                    /* 1 = this library was built with -DPKV_DEBUG */
 PKV_API int pkv_debug_topk_trace(void* device_u64x8); /* NULL disables; row 0 of every later top-k launch stamps 7 phase clocks */
 PKV_API int pkv_debug_wg_trace(void* device_u64);     /* NULL disables; 2*262144 u64: per-workgroup (start,end) wall clock, 100 MHz */
+/* Host-only route record of the last window-score call on this library (debug build; the release library answers
+ * PKV_ERR_UNSUPPORTED).  Copies min(n, 16) int32 words to `out`:
+ *   0 logits kernel (1 logits2_kernel, 2 logits_kernel, 3 the fp32 path)   1 instantiation (logits2: 0 window 8 / group 1,
+ *   1 one 16-column tile, 2 two; logits: MFMA k-steps 2/4/8)   2 logits tile (logits_kernel: 128/256 keys)   3 > 64 KB LDS opt-in
+ *   4 nst (logits2: 128-key stages per workgroup)   5 workgroups per head group (grid.x)   6 stages of the last workgroup
+ *   7 window keys straddle a stage boundary   8 ... a workgroup boundary   9 logits store mode   10 finalize_kernel window
+ *   constant (8, 32, 0 = run time)   11 positions per thread (4/8)   12 halo_spread   13 finalize blocks per row
+ *   14 nontemporal K loads   15 hardware exp2 in the partial statistics.  Words that do not apply are 0. */
+PKV_API int pkv_debug_score_route(int32_t* out, int n);
 /* Test hooks of the RELEASE library (tests/test_gpu_parity.py): two element-wise kernels that expose device functions the
  * hot kernels inline - the accurate exp() of finalize_kernel and the fp32 -> dtype rounding of every rounding point - so
  * that the suite checks the shipped code, not a copy.  Nothing on the product path launches them (~2 KB of code). */

@@ -12,6 +12,9 @@
 #include <vector>
 
 namespace pkv { thread_local KernelEvents* g_kev = nullptr; unsigned g_dyn_lds_epoch = 1; }
+#ifdef PKV_DEBUG
+namespace pkv { int g_score_route[SR_WORDS]; }
+#endif
 using namespace pkv;
 
 namespace {
@@ -194,7 +197,11 @@ int do_score_window(const pkv_desc* d, const void* q, const void* k, void* score
   lp.rcp_sqrt_d = d->dtype == PKV_F32 ? 1.0f / lp.sqrt_d : scale_multiplier(d->dtype, d->D, d->scale_mode);
   const int C = d->kv_group * d->window;
   int nT_used = L.nT;
+#ifdef PKV_DEBUG
+  memset(g_score_route, 0, sizeof(g_score_route));
+#endif
   if (d->dtype == PKV_F32) {
+    PKV_SCORE_ROUTE(SR_KERNEL, 3);
     lp.nT = L.nT;
     {
       ProfScope ps(PKV_K_LOGITS, st, true);
@@ -250,6 +257,14 @@ int do_score_window(const pkv_desc* d, const void* q, const void* k, void* score
     const size_t lbytes = (size_t)d->B * d->H * d->window * L.Sp * 2;
     lp.st_mode = lbytes < 0xffffffffull ? logits_store() : 0;                 // raw-buffer extent is 32-bit
     lp.logits_bytes = (uint32_t)std::min<size_t>(lbytes, 0xffffffffull);
+#ifdef PKV_DEBUG
+    {                                                                         // what logits2_kernel makes of nst (its `nh`, `edge`)
+      const int L0 = d->S - d->window, span = nst * 128;
+      PKV_SCORE_ROUTE(SR_NST, nst); PKV_SCORE_ROUTE(SR_LAST_NH, std::min(nst, (d->S - (lp.nT - 1) * span + 127) / 128));
+      PKV_SCORE_ROUTE(SR_STRADDLE_STAGE, L0 / 128 != (d->S - 1) / 128); PKV_SCORE_ROUTE(SR_STRADDLE_WG, L0 / span != (d->S - 1) / span);
+      PKV_SCORE_ROUTE(SR_ST_MODE, lp.st_mode); PKV_SCORE_ROUTE(SR_FEXP, lp.fexp);
+    }
+#endif
     ProfScope ps(PKV_K_LOGITS, st, true);
     hipError_t e = launch_logits2(d->dtype, lp, st);
     if (e != hipSuccess) return hip_fail(e);
@@ -834,10 +849,16 @@ int pkv_update_flatten_view(int32_t dtype, int32_t H, int32_t head_dim, const vo
 int pkv_debug_topk_trace(void* device_u64x8) { g_topk_trace = static_cast<unsigned long long*>(device_u64x8); return PKV_OK; }
 int pkv_debug_wg_trace(void* device_u64) { g_wg_trace = static_cast<unsigned long long*>(device_u64); return PKV_OK; }
 int pkv_debug_build(void) { return 1; }
+int pkv_debug_score_route(int32_t* out, int n) {
+  if (!out) return PKV_ERR_NULL;
+  for (int i = 0; i < n && i < SR_WORDS; ++i) out[i] = g_score_route[i];
+  return PKV_OK;
+}
 #else   // release library: the trace hooks do not exist in the kernels (see pkv_kernels.hpp)
 int pkv_debug_topk_trace(void* device_u64x8) { return device_u64x8 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_wg_trace(void* device_u64) { return device_u64 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_build(void) { return 0; }
+int pkv_debug_score_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
 #endif
 
 int pkv_runtime_reset(void) {

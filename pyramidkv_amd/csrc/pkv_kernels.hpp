@@ -61,6 +61,19 @@ inline hipError_t dyn_lds(const void* fn, size_t bytes) {
 #define PKV_TRACE(p) (static_cast<unsigned long long*>(nullptr))
 #endif
 
+// Route of the last window-score call (pkv_debug_score_route, debug build, host only): the launchers write the instantiation
+// they launch, do_score_window the rest.  Word order: include/pkv.h.
+enum ScoreRouteWord {
+  SR_KERNEL, SR_VARIANT, SR_TILE, SR_LDS_OPTIN, SR_NST, SR_NT, SR_LAST_NH, SR_STRADDLE_STAGE, SR_STRADDLE_WG, SR_ST_MODE,
+  SR_FIN_W, SR_FIN_PPT, SR_HALO_SPREAD, SR_FIN_BLOCKS, SR_NTLOAD, SR_FEXP, SR_WORDS
+};
+#ifdef PKV_DEBUG
+extern int g_score_route[SR_WORDS];
+#define PKV_SCORE_ROUTE(i, v) (pkv::g_score_route[(i)] = (v))
+#else
+#define PKV_SCORE_ROUTE(i, v) ((void)0)
+#endif
+
 struct LogitsParams {
   unsigned long long* wgtrace;   // debug: per-workgroup (start,end) wall clock, may be null
   const void* q;

@@ -729,10 +729,11 @@ hipError_t launch_logits2(int dtype, const LogitsParams& p, hipStream_t st) {
 #define PKV_L2(TT, NCT, NTL, WGC) PKV_KLAUNCH((logits2_kernel<TT, NCT, NTL, WGC>), grid, dim3(256), lds, st, p)
 #define PKV_L2D(TT, NTL)                                                                                   \
   do {                                                                                                     \
-    if (p.w == 8 && p.G == 1) PKV_L2(TT, 1, NTL, 8 * 256 + 1);                                             \
-    else if (nct == 1) PKV_L2(TT, 1, NTL, 0);                                                              \
-    else PKV_L2(TT, 2, NTL, 0);                                                                            \
+    if (p.w == 8 && p.G == 1) { PKV_SCORE_ROUTE(SR_VARIANT, 0); PKV_L2(TT, 1, NTL, 8 * 256 + 1); }               \
+    else if (nct == 1) { PKV_SCORE_ROUTE(SR_VARIANT, 1); PKV_L2(TT, 1, NTL, 0); }                                \
+    else { PKV_SCORE_ROUTE(SR_VARIANT, 2); PKV_L2(TT, 2, NTL, 0); }                                              \
   } while (0)
+  PKV_SCORE_ROUTE(SR_KERNEL, 1); PKV_SCORE_ROUTE(SR_NT, (int)grid.x); PKV_SCORE_ROUTE(SR_NTLOAD, p.nt ? 1 : 0);
   if (dtype == 0) { if (p.nt) PKV_L2D(BF16, true); else PKV_L2D(BF16, false); }
   else            { if (p.nt) PKV_L2D(F16, true); else PKV_L2D(F16, false); }
 #undef PKV_L2D
@@ -745,8 +746,11 @@ hipError_t launch_logits(int dtype, const LogitsParams& p, hipStream_t st) {
   dim3 grid(p.nT, p.B * (p.H / p.G));
   const int tile = p.tile;
   const size_t lds = (size_t)C * (tile + 8) * sizeof(uint16_t);
+  PKV_SCORE_ROUTE(SR_KERNEL, 2); PKV_SCORE_ROUTE(SR_TILE, tile); PKV_SCORE_ROUTE(SR_LDS_OPTIN, lds > 64 * 1024 ? 1 : 0); PKV_SCORE_ROUTE(SR_NT, (int)grid.x);
+  PKV_SCORE_ROUTE(SR_NTLOAD, p.nt ? 1 : 0);
 #define PKV_LAUNCH(TT, KPW, NT, KS)                                                                                     \
   do {                                                                                                                 \
+    PKV_SCORE_ROUTE(SR_VARIANT, KS);                                                                                         \
     if (lds > 64 * 1024) {  /* wide GQA groups x wide windows: opt in to more than 64 KB of dynamic LDS */           \
       hipError_t e_ = dyn_lds(reinterpret_cast<const void*>(logits_kernel<TT, KPW, NT, KS>), lds);                      \
       if (e_ != hipSuccess) return e_;                                                                                \
@@ -784,11 +788,13 @@ int finalize_blocks(int S, int w, int BH) { const int out = 256 * finalize_ppt(S
 hipError_t launch_finalize(int dtype, const FinalizeParams& p, hipStream_t st) {
   const int ppt = finalize_ppt(p.S, p.w, p.B * p.H);
   dim3 grid(finalize_blocks(p.S, p.w, p.B * p.H), p.B * p.H);
+  PKV_SCORE_ROUTE(SR_FIN_PPT, ppt); PKV_SCORE_ROUTE(SR_FIN_BLOCKS, (int)grid.x);
+  PKV_SCORE_ROUTE(SR_HALO_SPREAD, (p.w & (p.w - 1)) == 0 && p.w <= 64 ? 1 : 0);                 // finalize_kernel's halo_spread
 #define PKV_FIN2(TT, PP)                                                                                         \
   do {                                                                                                         \
-    if (p.w == 8) PKV_KLAUNCH((finalize_kernel<TT, 8, PP>), grid, dim3(256), 0, st, p);                        \
-    else if (p.w == 32) PKV_KLAUNCH((finalize_kernel<TT, 32, PP>), grid, dim3(256), 0, st, p);                 \
-    else PKV_KLAUNCH((finalize_kernel<TT, 0, PP>), grid, dim3(256), 0, st, p);                                 \
+    if (p.w == 8) { PKV_SCORE_ROUTE(SR_FIN_W, 8); PKV_KLAUNCH((finalize_kernel<TT, 8, PP>), grid, dim3(256), 0, st, p); }         \
+    else if (p.w == 32) { PKV_SCORE_ROUTE(SR_FIN_W, 32); PKV_KLAUNCH((finalize_kernel<TT, 32, PP>), grid, dim3(256), 0, st, p); } \
+    else { PKV_SCORE_ROUTE(SR_FIN_W, 0); PKV_KLAUNCH((finalize_kernel<TT, 0, PP>), grid, dim3(256), 0, st, p); }                  \
   } while (0)
 #define PKV_FIN(TT) do { if (ppt == 8) PKV_FIN2(TT, 8); else PKV_FIN2(TT, 4); } while (0)
   if (dtype == 0) PKV_FIN(BF16); else PKV_FIN(F16);
