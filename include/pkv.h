@@ -26,7 +26,8 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 202 /* 0.2.2: + pkv_debug_score_route; no layout change.
+#define PKV_VERSION 203 /* 0.2.3: + pkv_debug_merge_route, pkv_debug_unit_div; no layout change.
+                           0.2.2: + pkv_debug_score_route; no layout change.
                            0.2.1: + pkv_runtime_reset, pkv_debug_scale_multiplier; pkv_ada_budget_rows validates its host
                            mirror (8-byte aligned uint64 [H], host_seq >= 0) like pkv_ada_select; no layout change.  0.2.0: pkv_desc starts with struct_size (the struct can grow without breaking hosts built against an
                            older header); pkv_ada_select's budget step is one launch; host mirrors are uint64 [H] of
@@ -301,11 +302,30 @@ PKV_API int pkv_debug_wg_trace(void* device_u64);     /* NULL disables; 2*262144
  *   constant (8, 32, 0 = run time)   11 positions per thread (4/8)   12 halo_spread   13 finalize blocks per row
  *   14 nontemporal K loads   15 hardware exp2 in the partial statistics.  Words that do not apply are 0. */
 PKV_API int pkv_debug_score_route(int32_t* out, int n);
+/* Route record of the last pkv_merge_compact on this library (debug build; the release library answers PKV_ERR_UNSUPPORTED).
+ * Waits for the device, then copies min(n, 16) int32 words to `out`:
+ *   0 drop-list kernel (2 merge_droplist2_kernel, 1 merge_droplist_kernel)   1 its grid   2 pivot kernel (2 merge_pivot2_kernel,
+ *   1 merge_pivot_kernel, 3 merge_pivot_f32_kernel)   3 its KS (fp32: KSF)   4 pivot2: nontemporal row loads   5 pivot2: PF
+ *   6 pivot2: nst (128-row stages per workgroup)   7 pivot grid (workgroups)   8 workgroups per head (grid.x)   9 pivot2: stages
+ *   the last workgroup of a head would run over S rows   10 bucket fast path   11 bucket ranges (passes over the pivots)
+ *   12 scatter workgroup size   13 scatter bitmap bytes   14 ntp (row pitch of the unit-norm kept keys)
+ *   15 device flags: one bit per data-dependent path a merge kernel took (enum MergeFlag, pkv_kernels.hpp): 0 pivot2 signed-key
+ *   loop finished a stage, 1 pivot2 redo, 2 pivot2 exact keys by NaN, 3 bf16 multiply form, 4 bf16 div_const form, 5 a prefetch
+ *   was issued, 6 ragged workgroup, 7 workgroup past the drop list, 8 merge_pivot_kernel exact, 9 bucket fast, 10 bucket with
+ *   more than one range, 11 scatter group of 0 rows, 12 of more than 2048 rows, 13 / 14 a 64-row block with a tail of 1..31 /
+ *   33..63 rows, 15 a row whose maximum is zero was looked at again.  Words that do not apply are 0. */
+PKV_API int pkv_debug_merge_route(int32_t* out, int n);
 /* Test hooks of the RELEASE library (tests/test_gpu_parity.py): two element-wise kernels that expose device functions the
  * hot kernels inline - the accurate exp() of finalize_kernel and the fp32 -> dtype rounding of every rounding point - so
  * that the suite checks the shipped code, not a copy.  Nothing on the product path launches them (~2 KB of code). */
 PKV_API int pkv_debug_exp(const float* in, float* out, int64_t n, pkv_stream_t stream);
 PKV_API int pkv_debug_round(int32_t dtype, const float* in, void* out, int64_t n, pkv_stream_t stream);
+/* Test hook of the RELEASE library: "element / norm, rounded to the model dtype" of the LOOK-M merge in the three forms the merge
+ * kernels inline (pkv_common.hpp: unit_div, unit_div_const, unit_mul), element-wise over n (x, norm) pairs of 16-bit values
+ * (device pointers): out_div / out_divc / out_mul receive the rounded results, out_mul_ok[i] = 1 where merge_pivot2_kernel's
+ * guard lets a lane take the multiply form (bf16 only takes it; the guard itself is dtype-blind). */
+PKV_API int pkv_debug_unit_div(int32_t dtype, const void* x, const void* norm, void* out_div, void* out_divc, void* out_mul,
+                               void* out_mul_ok, int64_t n, pkv_stream_t stream);
 /* Host-only: the fp32 constant the bf16 / fp16 kernels multiply a logit by in place of "/ math.sqrt(head_dim)"
  * (pyramidkv_utils.py:317) for this dtype, head size and pkv_scale mode; tests/test_abi_and_host.py checks, over every finite
  * 16-bit input, that the multiply reproduces ATen's division ("div") / reciprocal multiply ("rcp") bit for bit. */

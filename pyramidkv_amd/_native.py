@@ -22,7 +22,7 @@ TIE = {"canonical": 0, "aten_rocm": 1}
 KERNEL_NAMES = ["logits", "finalize", "topk", "gather", "h2o_stats", "h2o_colsum", "sort", "budget"]
 
 
-PKV_VERSION = 202            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
+PKV_VERSION = 203            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
 
 
 class PkvDesc(C.Structure):
@@ -95,7 +95,9 @@ def _load():
         "pkv_debug_topk_trace": (C.c_int, [vp]),
         "pkv_debug_wg_trace": (C.c_int, [vp]),
         "pkv_debug_score_route": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+        "pkv_debug_merge_route": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
         "pkv_debug_exp": (C.c_int, [vp, vp, i64, vp]),
+        "pkv_debug_unit_div": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i64, vp]),
         "pkv_debug_round": (C.c_int, [i32, vp, vp, i64, vp]),
         "pkv_debug_scale_multiplier": (C.c_float, [i32, i32, i32]),
         "pkv_prof_enable": (C.c_int, [C.c_int]),

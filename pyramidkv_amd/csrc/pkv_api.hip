@@ -13,7 +13,7 @@
 
 namespace pkv { thread_local KernelEvents* g_kev = nullptr; unsigned g_dyn_lds_epoch = 1; }
 #ifdef PKV_DEBUG
-namespace pkv { int g_score_route[SR_WORDS]; }
+namespace pkv { int g_score_route[SR_WORDS]; int g_merge_route[MR_WORDS]; const unsigned int* g_merge_flags = nullptr; }
 #endif
 using namespace pkv;
 
@@ -854,11 +854,24 @@ int pkv_debug_score_route(int32_t* out, int n) {
   for (int i = 0; i < n && i < SR_WORDS; ++i) out[i] = g_score_route[i];
   return PKV_OK;
 }
+int pkv_debug_merge_route(int32_t* out, int n) {
+  if (!out) return PKV_ERR_NULL;
+  unsigned int flags = 0;
+  if (g_merge_flags) {
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(&flags, g_merge_flags, 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  g_merge_route[MR_FLAGS] = (int)flags;
+  for (int i = 0; i < n && i < MR_WORDS; ++i) out[i] = g_merge_route[i];
+  return PKV_OK;
+}
 #else   // release library: the trace hooks do not exist in the kernels (see pkv_kernels.hpp)
 int pkv_debug_topk_trace(void* device_u64x8) { return device_u64x8 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_wg_trace(void* device_u64) { return device_u64 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_build(void) { return 0; }
 int pkv_debug_score_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
+int pkv_debug_merge_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
 #endif
 
 int pkv_runtime_reset(void) {
@@ -876,6 +889,17 @@ int pkv_debug_exp(const float* in, float* out, int64_t n, pkv_stream_t stream) {
 int pkv_debug_round(int32_t dtype, const float* in, void* out, int64_t n, pkv_stream_t stream) {
   if (dtype != PKV_BF16 && dtype != PKV_F16) return PKV_ERR_DTYPE;
   hipError_t e = launch_debug_round(dtype, in, static_cast<uint16_t*>(out), n, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PKV_OK : hip_fail(e);
+}
+
+int pkv_debug_unit_div(int32_t dtype, const void* x, const void* norm, void* out_div, void* out_divc, void* out_mul, void* out_mul_ok,
+                       int64_t n, pkv_stream_t stream) {
+  if (dtype != PKV_BF16 && dtype != PKV_F16) return PKV_ERR_DTYPE;
+  if (!x || !norm || !out_div || !out_divc || !out_mul || !out_mul_ok) return PKV_ERR_NULL;
+  if (n < 1) return PKV_ERR_SHAPE;
+  hipError_t e = launch_debug_unit_div(dtype, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(norm), static_cast<uint16_t*>(out_div),
+                                       static_cast<uint16_t*>(out_divc), static_cast<uint16_t*>(out_mul), static_cast<uint8_t*>(out_mul_ok), n,
+                                       static_cast<hipStream_t>(stream));
   return e == hipSuccess ? PKV_OK : hip_fail(e);
 }
 

@@ -138,6 +138,16 @@ __device__ __forceinline__ float div_const(float x, float c, float rc) {
   return fmaf(r, rc, q);
 }
 
+// "element / norm, rounded to the model dtype" of the LOOK-M merge (reference pyramidkv_utils.py:150) in its three forms; x is a
+// model-dtype element, n the row's norm already rounded to the model dtype, rn = RN(1 / n).  The results are about to be rounded
+// to the model dtype (round_pack2).  pkv_debug_unit_div runs all three over given (x, n) pairs; tests/test_gpu_merge_routes.py
+// compares them with the division over every 16-bit x and every significand of n.
+__device__ __forceinline__ float unit_div(float x, float n) { return x / n; }                                  // merge_targets_kernel
+__device__ __forceinline__ float unit_div_const(float x, float n, float rn) { return div_const(x, n, rn); }    // both pivot kernels
+__device__ __forceinline__ float unit_mul(float x, float rn) { return x * rn; }                                // merge_pivot2_kernel, bf16
+// the lane's part of merge_pivot2_kernel's wave-wide guard: the multiply form is only taken when NO lane of the wave says no
+__device__ __forceinline__ bool unit_mul_refused(float n, bool bad) { return bad || !(n >= 1.17549435e-38f); }
+
 // "attn / math.sqrt(head_dim)" (reference pyramidkv_utils.py:317) on a value already rounded to the model dtype, result
 // about to be rounded to the model dtype again: ONE multiply by a host-chosen constant `rc` in both scale modes
 // (pkv_api.hip scale_multiplier; exhaustive checks over every finite 16-bit input in tests/test_abi_and_host.py):

@@ -74,6 +74,42 @@ extern int g_score_route[SR_WORDS];
 #define PKV_SCORE_ROUTE(i, v) ((void)0)
 #endif
 
+// Route of the last LOOK-M merge (pkv_debug_merge_route, debug build): launch_merge and launch_merge_t / launch_merge_f32_t
+// write the host's choices; the last word is read back from the device, where the merge kernels of the debug build OR one bit
+// per data-dependent path into the spare word behind MergeParams::ndrop (the workspace layout is the release one: the ndrop
+// slot is 256 bytes, 4 of them used).  Word order: include/pkv.h.
+enum MergeRouteWord {
+  MR_DROPLIST, MR_DROP_GRID, MR_PIVOT, MR_KS, MR_NT_LOAD, MR_PF, MR_NST, MR_PIVOT_GRID, MR_WG_PER_HEAD, MR_LAST_NH,
+  MR_BUCKET_FAST, MR_BUCKET_RANGES, MR_SCATTER_BLOCK, MR_BITMAP_BYTES, MR_NTP, MR_FLAGS, MR_WORDS
+};
+enum MergeFlag : unsigned int {
+  MF_P2_SIGNED = 1u << 0,        // merge_pivot2_kernel: a stage finished on the signed-integer key loop
+  MF_P2_REDO = 1u << 1,          // ... was redone with the exact keys (a row's maximum not above +0)
+  MF_P2_NAN_EXACT = 1u << 2,     // ... took the exact keys because of kept_bad / a bad row in the wave
+  MF_P2_MUL = 1u << 3,           // bf16: unit rows by multiplication with the reciprocal
+  MF_P2_DIVC = 1u << 4,          // bf16: unit rows by div_const (a zero / subnormal / non-finite norm in the wave)
+  MF_P2_PREFETCH = 1u << 5,      // a prefetch was issued inside stage() (s + PF < nh)
+  MF_P2_RAGGED = 1u << 6,        // a workgroup with nh < nst
+  MF_P2_PAST_END = 1u << 7,      // a workgroup past the end of the drop list
+  MF_P1_EXACT = 1u << 8,         // merge_pivot_kernel with the NaN-exact keys
+  MF_BUCKET_FAST = 1u << 9,
+  MF_BUCKET_RANGES = 1u << 10,   // the ranged path with more than one range
+  MF_SC_GROUP0 = 1u << 11,       // merge_scatter_kernel: a kept row nothing merges into
+  MF_SC_OVER_CAP = 1u << 12,     // ... a group of more than MS_CAP rows (several list passes)
+  MF_SC_TAIL_LO = 1u << 13,      // ... a 64-row block with a tail of 1..31 rows
+  MF_SC_TAIL_HI = 1u << 14,      // ... of 33..63 rows
+  MF_ZERO_LOOK = 1u << 15,       // a row whose maximum is zero was looked at again (first zero of either sign wins)
+};
+#ifdef PKV_DEBUG
+extern int g_merge_route[MR_WORDS];
+extern const unsigned int* g_merge_flags;      // device address of the flags word of the last merge
+#define PKV_MERGE_ROUTE(i, v) (pkv::g_merge_route[(i)] = (int)(v))
+#define PKV_MERGE_FLAG(p, bit) atomicOr(reinterpret_cast<unsigned int*>((p).ndrop) + 1, (unsigned int)(bit))
+#else
+#define PKV_MERGE_ROUTE(i, v) ((void)0)
+#define PKV_MERGE_FLAG(p, bit) ((void)0)
+#endif
+
 struct LogitsParams {
   unsigned long long* wgtrace;   // debug: per-workgroup (start,end) wall clock, may be null
   const void* q;
@@ -274,6 +310,8 @@ hipError_t launch_merge(int dtype, const MergeParams& p, hipStream_t st);
 size_t merge_max_seq();      // longest sequence the merge takes (LDS bitmap of the scatter kernel)
 hipError_t launch_debug_exp(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_round(int dtype, const float* in, uint16_t* out, int64_t n, hipStream_t st);
+hipError_t launch_debug_unit_div(int dtype, const uint16_t* x, const uint16_t* nrm, uint16_t* out_div, uint16_t* out_divc, uint16_t* out_mul,
+                                 uint8_t* out_mul_ok, int64_t n, hipStream_t st);
 // fp32 tensors (pkv_f32.hip)
 hipError_t launch_logits_f32(const LogitsParams& p, hipStream_t st);
 hipError_t launch_finalize_f32(const FinalizeParams& p, hipStream_t st);

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 namespace pkv {
@@ -175,9 +176,9 @@ __global__ __launch_bounds__(256) void merge_targets_kernel(MergeParams p) {
   // similarities in its inner loop (torch.max's rules); otherwise every similarity of the head is finite and it skips that
   if (lane == 0 && (!(n2 < INFINITY) || !(n > 0.f))) atomicOr(p.kept_bad + bh, 1);
   uint16_t* dst = reinterpret_cast<uint16_t*>(p.tn) + ((int64_t)bh * p.ntp + j) * D + lane * EPL;
-  if constexpr (EPL == 1) dst[0] = Elem<T>::from_f32(x[0] / n);                     // k / norm -> model dtype
-  else if constexpr (EPL == 2) *reinterpret_cast<uint32_t*>(dst) = round_pack2<T>(x[0] / n, x[1] / n);
-  else *reinterpret_cast<uint2*>(dst) = make_uint2(round_pack2<T>(x[0] / n, x[1] / n), round_pack2<T>(x[2] / n, x[3] / n));
+  if constexpr (EPL == 1) dst[0] = Elem<T>::from_f32(unit_div(x[0], n));                     // k / norm -> model dtype
+  else if constexpr (EPL == 2) *reinterpret_cast<uint32_t*>(dst) = round_pack2<T>(unit_div(x[0], n), unit_div(x[1], n));
+  else *reinterpret_cast<uint2*>(dst) = make_uint2(round_pack2<T>(unit_div(x[0], n), unit_div(x[1], n)), round_pack2<T>(unit_div(x[2], n), unit_div(x[3], n)));
 }
 
 // ---- 4. pivot: for every dropped row the kept row with the largest cosine similarity (first maximum) ----
@@ -190,6 +191,13 @@ template <int KS> struct MergeShape {
   static constexpr int ITER = KS == 8 ? 2 : 4;       // passes per workgroup (64 dropped rows each): A operands = ITER x KS x 4 registers
   static constexpr int TROW = D + 8;                 // LDS row stride in elements (+16 B: the 16 rows of a B fragment hit different banks)
 };
+
+// two packed 16-bit similarities with -0 (0x8000) folded onto +0: torch.max compares values, the first zero of either sign wins
+__device__ __forceinline__ uint32_t fold_neg_zero_pk(uint32_t pk) {
+  if ((pk & 0x0000ffffu) == 0x00008000u) pk &= 0xffff0000u;
+  if ((pk & 0xffff0000u) == 0x80000000u) pk &= 0x0000ffffu;
+  return pk;
+}
 
 template <typename T, int KS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? 3 : 4))) void merge_pivot_kernel(MergeParams p) {
@@ -237,10 +245,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? 3
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) {
       u32x4 a;
-      a.x = round_pack2<T>(div_const(xs[kk * 8 + 0], nr, rn), div_const(xs[kk * 8 + 1], nr, rn));
-      a.y = round_pack2<T>(div_const(xs[kk * 8 + 2], nr, rn), div_const(xs[kk * 8 + 3], nr, rn));
-      a.z = round_pack2<T>(div_const(xs[kk * 8 + 4], nr, rn), div_const(xs[kk * 8 + 5], nr, rn));
-      a.w = round_pack2<T>(div_const(xs[kk * 8 + 6], nr, rn), div_const(xs[kk * 8 + 7], nr, rn));
+      a.x = round_pack2<T>(unit_div_const(xs[kk * 8 + 0], nr, rn), unit_div_const(xs[kk * 8 + 1], nr, rn));
+      a.y = round_pack2<T>(unit_div_const(xs[kk * 8 + 2], nr, rn), unit_div_const(xs[kk * 8 + 3], nr, rn));
+      a.z = round_pack2<T>(unit_div_const(xs[kk * 8 + 4], nr, rn), unit_div_const(xs[kk * 8 + 5], nr, rn));
+      a.w = round_pack2<T>(unit_div_const(xs[kk * 8 + 6], nr, rn), unit_div_const(xs[kk * 8 + 7], nr, rn));
       af[it][kk] = a;
     }
   }
@@ -249,65 +257,85 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? 3
   // is ONE unsigned word whose maximum is torch.max's answer (:151): the larger value, ties to the FIRST column; a NaN
   // similarity (zero-norm row: 0/0 at :146) gets the largest key, so it ranks above everything and the first NaN wins, as
   // torch.max propagates it.  One v_max_u32 per similarity instead of compare + two selects, half the registers.
+  // torch.max compares VALUES: -0 == +0, the first zero of either sign wins, while the keys rank +0 (0x8000) above -0 (0x7fff).
+  // That only matters for a row whose maximum is zero, so the loop stays as it is and a row whose best key turns out to be the key
+  // of +0 is looked at again (all waves of the workgroup together: the tiles go through shared LDS) with -0 folded onto +0.
   uint32_t bestk[MP_ITER][4];
-#pragma unroll
-  for (int it = 0; it < MP_ITER; ++it)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bestk[it][r] = 0u;
 
   // NaN similarities can only come from a unit-norm row that is not finite: without one in reach (the usual case) the
   // NaN canonicalisation is skipped - the loop is bound by its vector instructions per similarity
-  const bool exact = p.kept_bad[bh] != 0 || __ballot(bad_row) != 0ull;     // wave-uniform
-  for (int t0 = 0; t0 < nt; t0 += MP_TN) {
-    const int tcnt = min(MP_TN, nt - t0);
-    __syncthreads();
-    for (int c = tid; c < MP_TN * CPR; c += 256) {                        // 16-B chunks; rows past tcnt are zero
-      const int rr = c / CPR, ch = c - rr * CPR;
-      uint4 val = make_uint4(0, 0, 0, 0);
-      if (rr < tcnt) val = reinterpret_cast<const uint4*>(tn + (int64_t)(t0 + rr) * D)[ch];
-      *reinterpret_cast<uint4*>(tile + rr * MP_TROW + ch * 8) = val;
-    }
-    __syncthreads();
-    for (int n16 = 0; n16 * 16 < tcnt; ++n16) {
-      u32x4 bf[KS];
+  bool exact = p.kept_bad[bh] != 0 || __ballot(bad_row) != 0ull;           // wave-uniform: NaN and -0 canonicalised
+  if (exact && lane == 0) PKV_MERGE_FLAG(p, MF_P1_EXACT);
+#pragma nounroll
+  for (int look = 0; look < 2; ++look) {
 #pragma unroll
-      for (int kk = 0; kk < KS; ++kk) bf[kk] = *reinterpret_cast<const u32x4*>(tile + (n16 * 16 + li) * MP_TROW + kk * 32 + lg * 8);
-      const int col = t0 + n16 * 16 + li;
-      const uint32_t colkey = col < t0 + tcnt ? 0xffffu - (uint32_t)col : 0xffffffffu;   // all ones: a column past the tile (masked below)
+    for (int it = 0; it < MP_ITER; ++it)
 #pragma unroll
-      for (int it = 0; it < MP_ITER; ++it) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int r = 0; r < 4; ++r) bestk[it][r] = 0u;
+    for (int t0 = 0; t0 < nt; t0 += MP_TN) {
+      const int tcnt = min(MP_TN, nt - t0);
+      __syncthreads();
+      for (int c = tid; c < MP_TN * CPR; c += 256) {                        // 16-B chunks; rows past tcnt are zero
+        const int rr = c / CPR, ch = c - rr * CPR;
+        uint4 val = make_uint4(0, 0, 0, 0);
+        if (rr < tcnt) val = reinterpret_cast<const uint4*>(tn + (int64_t)(t0 + rr) * D)[ch];
+        *reinterpret_cast<uint4*>(tile + rr * MP_TROW + ch * 8) = val;
+      }
+      __syncthreads();
+      for (int n16 = 0; n16 * 16 < tcnt; ++n16) {
+        u32x4 bf[KS];
 #pragma unroll
-        for (int kk = 0; kk < KS; ++kk) acc = Mfma<T>::run(af[it][kk], bf[kk], acc);
-        uint32_t pk[2] = {round_pack2<T>(acc[0], acc[1]), round_pack2<T>(acc[2], acc[3])};   // similarities in the model dtype (:150)
+        for (int kk = 0; kk < KS; ++kk) bf[kk] = *reinterpret_cast<const u32x4*>(tile + (n16 * 16 + li) * MP_TROW + kk * 32 + lg * 8);
+        const int col = t0 + n16 * 16 + li;
+        const uint32_t colkey = col < t0 + tcnt ? 0xffffu - (uint32_t)col : 0xffffffffu;   // all ones: a column past the tile (masked below)
 #pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          // both halves at once: sign-magnitude -> unsigned order (negative: all bits flipped, else the sign bit set)
-          const uint32_t neg = (pk[h2] >> 15) & 0x00010001u;
-          uint32_t m = pk[h2] ^ ((neg * 0xffffu) | 0x80008000u);
-          if (exact) {
-            if (Elem<T>::is_nan((uint16_t)(pk[h2] & 0xffffu))) m |= 0x0000ffffu;
-            if (Elem<T>::is_nan((uint16_t)(pk[h2] >> 16))) m |= 0xffff0000u;
-          }
-          const uint32_t k0 = (m << 16) | colkey, k1 = (m & 0xffff0000u) | colkey;
-          if (colkey != 0xffffffffu) {
-            bestk[it][2 * h2] = max(bestk[it][2 * h2], k0);
-            bestk[it][2 * h2 + 1] = max(bestk[it][2 * h2 + 1], k1);
+        for (int it = 0; it < MP_ITER; ++it) {
+          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kk = 0; kk < KS; ++kk) acc = Mfma<T>::run(af[it][kk], bf[kk], acc);
+          uint32_t pk[2] = {round_pack2<T>(acc[0], acc[1]), round_pack2<T>(acc[2], acc[3])};   // similarities in the model dtype (:150)
+#pragma unroll
+          for (int h2 = 0; h2 < 2; ++h2) {
+            if (exact) pk[h2] = fold_neg_zero_pk(pk[h2]);
+            // both halves at once: sign-magnitude -> unsigned order (negative: all bits flipped, else the sign bit set)
+            const uint32_t neg = (pk[h2] >> 15) & 0x00010001u;
+            uint32_t m = pk[h2] ^ ((neg * 0xffffu) | 0x80008000u);
+            if (exact) {
+              if (Elem<T>::is_nan((uint16_t)(pk[h2] & 0xffffu))) m |= 0x0000ffffu;
+              if (Elem<T>::is_nan((uint16_t)(pk[h2] >> 16))) m |= 0xffff0000u;
+            }
+            const uint32_t k0 = (m << 16) | colkey, k1 = (m & 0xffff0000u) | colkey;
+            if (colkey != 0xffffffffu) {
+              bestk[it][2 * h2] = max(bestk[it][2 * h2], k0);
+              bestk[it][2 * h2 + 1] = max(bestk[it][2 * h2 + 1], k1);
+            }
           }
         }
       }
     }
+    // first maximum across the 16 columns (lanes of one lg group): the largest key
+    bool zero_max = false;
+#pragma unroll
+    for (int it = 0; it < MP_ITER; ++it) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        uint32_t kx = bestk[it][r];
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) kx = max(kx, (uint32_t)__shfl_xor((int)kx, o, 64));
+        bestk[it][r] = kx;
+        zero_max |= (kx >> 16) == 0x8000u;                                  // the row's maximum is +0: a -0 may stand before it
+      }
+    }
+    if (!__syncthreads_or(look == 0 && !exact && zero_max)) break;          // every wave asks: the second look is the workgroup's
+    if (tid == 0) PKV_MERGE_FLAG(p, MF_ZERO_LOOK);
+    exact = true;
   }
-  // first maximum across the 16 columns (lanes of one lg group): the largest key
 #pragma unroll
   for (int it = 0; it < MP_ITER; ++it) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      uint32_t kx = bestk[it][r];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) kx = max(kx, (uint32_t)__shfl_xor((int)kx, o, 64));
       const int row = row_wg + it * MP_ROWS + wave * 16 + lg * 4 + r;
-      if (li == 0 && row < n) p.pivot[(int64_t)bh * p.S + row] = (int32_t)(0xffffu - (kx & 0xffffu));
+      if (li == 0 && row < n) p.pivot[(int64_t)bh * p.S + row] = (int32_t)(0xffffu - (bestk[it][r] & 0xffffu));
     }
   }
 }
@@ -330,7 +358,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? 3
 //   * arg-max keys: raw 16-bit pattern << 16 | (0xffff - column) compared as SIGNED integers orders all non-negative
 //     similarities correctly and puts every negative one below them; a row whose maximum is not above +0 (or a wave that can
 //     see a NaN) is redone with the exact order-preserving keys of the kernel above (wave-uniform, ~never for real keys: the
-//     observation-window rows are among the kept rows).
+//     observation-window rows are among the kept rows).  The exact keys fold -0 onto +0: zero as the maximum goes to the FIRST zero.
 constexpr int MP2_TN = 144;               // kept rows of the one LDS tile: [MP2_TN][16 chunks of 16 B], chunk c of row r at slot c ^ (r & 15)
 constexpr int MP2_HT = 128;               // dropped rows per stage (4 waves x 32)
 constexpr int MP2_STAGE_BYTES = 4 * 4096; // wave-private transpose areas: 16 rows x 256 B each (a stage goes through in two halves)
@@ -364,8 +392,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 3
   const int bh = blockIdx.y, b = bh / p.H, h = bh - b * p.H, hk = h / p.G;
   const int n = *p.ndrop;
   const int row_wg = blockIdx.x * nst * MP2_HT;
-  if (row_wg >= n) return;
+  if (row_wg >= n) {
+    if (tid == 0) PKV_MERGE_FLAG(p, MF_P2_PAST_END);
+    return;
+  }
   const int nh = min(nst, (n - row_wg + MP2_HT - 1) / MP2_HT);
+  if (tid == 0 && nh < nst) PKV_MERGE_FLAG(p, MF_P2_RAGGED);
   const int nt = p.k + p.w;                                                     // <= MP2_TN (launch_merge_t)
   const uint16_t* kbase = reinterpret_cast<const uint16_t*>(p.kptr) + (int64_t)b * p.ks_b + (int64_t)hk * p.ks_h;
   const uint16_t* tn = reinterpret_cast<const uint16_t*>(p.tn) + (int64_t)bh * p.ntp * D;
@@ -433,6 +465,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 3
 #pragma unroll
     for (int j = 0; j < 4; ++j) kst[j * 64 + lane] = pre[4 + j];                // rows 16..31
     if (s + PF < nh) {
+      if (lane == 0) PKV_MERGE_FLAG(p, MF_P2_PREFETCH);
       issue_rows(idn, pre);
       if (s + PF + 1 < nh) issue_idx(s + PF + 1, idn);
     }
@@ -465,30 +498,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 3
       const float rn = 1.0f / nr;
       bool divide = true;
       if constexpr (std::is_same<T, BF16>::value)                              // bf16 (see the head of this kernel)
-        divide = __ballot(bad || !(nr >= 1.17549435e-38f)) != 0ull;
+        divide = __ballot(unit_mul_refused(nr, bad)) != 0ull;
+      if (std::is_same<T, BF16>::value && lane == 0) PKV_MERGE_FLAG(p, divide ? MF_P2_DIVC : MF_P2_MUL);
       if (divide) {
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
           u32x4 a;
-          a.x = round_pack2<T>(div_const(xs[kk * 8 + 0], nr, rn), div_const(xs[kk * 8 + 1], nr, rn));
-          a.y = round_pack2<T>(div_const(xs[kk * 8 + 2], nr, rn), div_const(xs[kk * 8 + 3], nr, rn));
-          a.z = round_pack2<T>(div_const(xs[kk * 8 + 4], nr, rn), div_const(xs[kk * 8 + 5], nr, rn));
-          a.w = round_pack2<T>(div_const(xs[kk * 8 + 6], nr, rn), div_const(xs[kk * 8 + 7], nr, rn));
+          a.x = round_pack2<T>(unit_div_const(xs[kk * 8 + 0], nr, rn), unit_div_const(xs[kk * 8 + 1], nr, rn));
+          a.y = round_pack2<T>(unit_div_const(xs[kk * 8 + 2], nr, rn), unit_div_const(xs[kk * 8 + 3], nr, rn));
+          a.z = round_pack2<T>(unit_div_const(xs[kk * 8 + 4], nr, rn), unit_div_const(xs[kk * 8 + 5], nr, rn));
+          a.w = round_pack2<T>(unit_div_const(xs[kk * 8 + 6], nr, rn), unit_div_const(xs[kk * 8 + 7], nr, rn));
           af[t][kk] = a;
         }
       } else {
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
           u32x4 a;
-          a.x = round_pack2<T>(xs[kk * 8 + 0] * rn, xs[kk * 8 + 1] * rn);
-          a.y = round_pack2<T>(xs[kk * 8 + 2] * rn, xs[kk * 8 + 3] * rn);
-          a.z = round_pack2<T>(xs[kk * 8 + 4] * rn, xs[kk * 8 + 5] * rn);
-          a.w = round_pack2<T>(xs[kk * 8 + 6] * rn, xs[kk * 8 + 7] * rn);
+          a.x = round_pack2<T>(unit_mul(xs[kk * 8 + 0], rn), unit_mul(xs[kk * 8 + 1], rn));
+          a.y = round_pack2<T>(unit_mul(xs[kk * 8 + 2], rn), unit_mul(xs[kk * 8 + 3], rn));
+          a.z = round_pack2<T>(unit_mul(xs[kk * 8 + 4], rn), unit_mul(xs[kk * 8 + 5], rn));
+          a.w = round_pack2<T>(unit_mul(xs[kk * 8 + 6], rn), unit_mul(xs[kk * 8 + 7], rn));
           af[t][kk] = a;
         }
       }
     }
     bool exact = kept_bad || __ballot(bad_row) != 0ull;                         // wave-uniform
+    if (exact && lane == 0) PKV_MERGE_FLAG(p, MF_P2_NAN_EXACT);
     uint32_t res[2][4];                                                         // low 16 bits: 0xffff - kept-row number of the first maximum
     if (!exact) {
       int best[2][4];
@@ -556,6 +591,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 3
           res[t][r] = (uint32_t)kx;
         }
       exact = __ballot(redo) != 0ull;
+      if (lane == 0) PKV_MERGE_FLAG(p, exact ? MF_P2_REDO : MF_P2_SIGNED);
     }
     if (exact) {                                                                // merge_pivot_kernel's keys: total order incl. negative values, NaN first
       uint32_t bestk[2][4];
@@ -577,6 +613,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PF == 1 ? 3
           uint32_t pk[2] = {round_pack2<T>(acc[0], acc[1]), round_pack2<T>(acc[2], acc[3])};
 #pragma unroll
           for (int h2 = 0; h2 < 2; ++h2) {
+            pk[h2] = fold_neg_zero_pk(pk[h2]);                                  // a zero maximum: the first zero of either sign (torch.max)
             const uint32_t neg = (pk[h2] >> 15) & 0x00010001u;
             uint32_t m = pk[h2] ^ ((neg * 0xffffu) | 0x80008000u);
             if (Elem<T>::is_nan((uint16_t)(pk[h2] & 0xffffu))) m |= 0x0000ffffu;
@@ -629,6 +666,7 @@ __global__ __launch_bounds__(1024) void merge_bucket_kernel(MergeParams p, int f
   const int32_t* piv = p.pivot + (int64_t)bh * p.S;
   int32_t* list = p.blist + (int64_t)bh * p.S;
   int32_t* start = p.bstart + (int64_t)bh * (nt + 1);
+  if (tid == 0) PKV_MERGE_FLAG(p, fast ? MF_BUCKET_FAST : (nt > MB_RANGE ? MF_BUCKET_RANGES : 0));
   if (fast) {                                                             // host: nt * 32 <= MB_RANGE && S <= 32768
     // the usual size (round 6): every thread keeps its <= 32 pivots and positions in registers (all loads of the kernel leave
     // together), and every counter exists 32 times - copy (lane & 31) sits in bank (lane & 31), so the 64 atomics of a wave
@@ -757,6 +795,7 @@ __global__ __launch_bounds__(KS * 32) void merge_scatter_kernel(MergeParams p) {
   const uint32_t traw = *reinterpret_cast<const uint32_t*>(base + (int64_t)tpos * sstride + d);   // the kept row BEFORE merging (gather at :157/:160)
   const pkv_f32x2 t = {Elem<T>::to_f32((uint16_t)(traw & 0xffffu)), Elem<T>::to_f32((uint16_t)(traw >> 16))};
   pkv_f32x2 acc = t;                                                      // include_self
+  if (tid == 0) PKV_MERGE_FLAG(p, m == 0 ? MF_SC_GROUP0 : (m > MS_CAP ? MF_SC_OVER_CAP : 0));
   if (m > 0) {                                                            // workgroup-uniform
     const int nw = (p.S + 31) >> 5;
     for (int wd = tid; wd < nw; wd += NTH) ms_bitmap[wd] = 0u;
@@ -798,6 +837,7 @@ __global__ __launch_bounds__(KS * 32) void merge_scatter_kernel(MergeParams p) {
       for (uint32_t l64 = 0; l64 < mm; l64 += 64) {
         const int myrow = lst[l64 + (uint32_t)lane < mm ? l64 + (uint32_t)lane : mm - 1];
         const uint32_t left = mm - l64 < 64u ? mm - l64 : 64u;
+        if (tid == 0 && left != 64u && left != 32u) PKV_MERGE_FLAG(p, left < 32u ? MF_SC_TAIL_LO : MF_SC_TAIL_HI);
         for (uint32_t b0 = 0; b0 < left; b0 += MS_B) {
           uint32_t x[MS_B];
 #pragma unroll
@@ -863,6 +903,9 @@ hipError_t launch_merge_t(const MergeParams& p, hipStream_t st) {
       }
       const dim3 g2((p.S + nst * MP2_HT - 1) / (nst * MP2_HT), p.B * p.H);
       const size_t lds = MP2_LDS_BYTES;
+      PKV_MERGE_ROUTE(MR_PIVOT, 2); PKV_MERGE_ROUTE(MR_NT_LOAD, merge_pivot2_nt() ? 1 : 0); PKV_MERGE_ROUTE(MR_PF, merge_pivot2_pf() == 2 ? 2 : 1);
+      PKV_MERGE_ROUTE(MR_NST, nst); PKV_MERGE_ROUTE(MR_PIVOT_GRID, (int64_t)g2.x * g2.y); PKV_MERGE_ROUTE(MR_WG_PER_HEAD, g2.x);
+      PKV_MERGE_ROUTE(MR_LAST_NH, std::min<int64_t>(nst, (p.S - (int64_t)(g2.x - 1) * nst * MP2_HT + MP2_HT - 1) / MP2_HT));
       hipError_t e = hipSuccess;
 #define PKV_MP2(NTL, PFD)                                                                                   \
   do {                                                                                                      \
@@ -876,9 +919,14 @@ hipError_t launch_merge_t(const MergeParams& p, hipStream_t st) {
       pipelined = true;
     }
   }
-  if (!pipelined) hipLaunchKernelGGL((merge_pivot_kernel<T, KS>), gp, dim3(256), 0, st, p);
+  if (!pipelined) {
+    PKV_MERGE_ROUTE(MR_PIVOT, 1); PKV_MERGE_ROUTE(MR_PIVOT_GRID, (int64_t)gp.x * gp.y); PKV_MERGE_ROUTE(MR_WG_PER_HEAD, gp.x);
+    hipLaunchKernelGGL((merge_pivot_kernel<T, KS>), gp, dim3(256), 0, st, p);
+  }
+  PKV_MERGE_ROUTE(MR_KS, KS); PKV_MERGE_ROUTE(MR_SCATTER_BLOCK, KS * 32); PKV_MERGE_ROUTE(MR_BITMAP_BYTES, bitmap_bytes);
   {
     const int fast = (nt * 32 <= MB_RANGE && p.S <= 32768) ? 1 : 0;
+    PKV_MERGE_ROUTE(MR_BUCKET_FAST, fast); PKV_MERGE_ROUTE(MR_BUCKET_RANGES, fast ? 1 : (nt + MB_RANGE - 1) / MB_RANGE);
     const size_t blds = fast ? (size_t)32768 * 2 : 0;
     if (fast) {
       const hipError_t eb = dyn_lds(reinterpret_cast<const void*>(merge_bucket_kernel), blds);
@@ -923,6 +971,7 @@ __global__ __launch_bounds__(256) void merge_targets_f32_kernel(MergeParams p) {
 // order-preserving 32-bit key of an fp32 similarity; NaN ranks above everything (torch.max propagates the first NaN)
 __device__ __forceinline__ uint32_t sim_key_f32(float x) {
   if (x != x) return 0xffffffffu;
+  if (x == 0.f) return 0x80000000u;                                        // -0 == +0: the first zero wins (torch.max compares values)
   const uint32_t u = __float_as_uint(x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -1075,8 +1124,11 @@ hipError_t launch_merge_f32_t(const MergeParams& p, hipStream_t st) {
   const size_t bitmap_bytes = (size_t)((p.S + 31) / 32) * 4;
   hipLaunchKernelGGL((merge_targets_f32_kernel<KSF>), gt, dim3(256), 0, st, p);
   hipLaunchKernelGGL((merge_pivot_f32_kernel<KSF>), gp, dim3(256), 0, st, p);
+  PKV_MERGE_ROUTE(MR_PIVOT, 3); PKV_MERGE_ROUTE(MR_KS, KSF); PKV_MERGE_ROUTE(MR_PIVOT_GRID, (int64_t)gp.x * gp.y); PKV_MERGE_ROUTE(MR_WG_PER_HEAD, gp.x);
+  PKV_MERGE_ROUTE(MR_SCATTER_BLOCK, 2 * D); PKV_MERGE_ROUTE(MR_BITMAP_BYTES, bitmap_bytes);
   {
     const int fast = (nt * 32 <= MB_RANGE && p.S <= 32768) ? 1 : 0;
+    PKV_MERGE_ROUTE(MR_BUCKET_FAST, fast); PKV_MERGE_ROUTE(MR_BUCKET_RANGES, fast ? 1 : (nt + MB_RANGE - 1) / MB_RANGE);
     const size_t blds = fast ? (size_t)32768 * 2 : 0;
     if (fast) {
       const hipError_t eb = dyn_lds(reinterpret_cast<const void*>(merge_bucket_kernel), blds);
@@ -1088,16 +1140,53 @@ hipError_t launch_merge_f32_t(const MergeParams& p, hipStream_t st) {
   return hipGetLastError();
 }
 
+// pkv_debug_unit_div: the three unit-row division forms of pkv_common.hpp on given (element, norm) pairs, each rounded to the
+// model dtype as the kernels round them, and what merge_pivot2_kernel's guard says about the pair
+template <typename T>
+__global__ __launch_bounds__(256) void debug_unit_div_kernel(const uint16_t* x, const uint16_t* nrm, uint16_t* out_div, uint16_t* out_divc,
+                                                             uint16_t* out_mul, uint8_t* out_mul_ok, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float xv = Elem<T>::to_f32(x[i]), nr = Elem<T>::to_f32(nrm[i]);
+    const bool bad = !(nr < INFINITY) || !(nr > 0.f);
+    const float rn = 1.0f / nr;
+    // The kernels round an fp32 value to the model dtype with v_cvt_pk_* (round_pack2 of two live values).  For a single value the
+    // compiler would fold the last fp32 operation INTO the conversion (v_fma_mixlo_f16: one rounding of the exact result instead of
+    // fp32 then fp16 - it differs where the fp32 result sits on an fp16 rounding tie), so the fp32 results are pinned in registers first.
+    float d = unit_div(xv, nr), dc = unit_div_const(xv, nr, rn), m = unit_mul(xv, rn);
+    asm volatile("" : "+v"(d), "+v"(dc), "+v"(m));
+    out_div[i] = (uint16_t)(round_pack2<T>(d, 0.f) & 0xffffu);
+    out_divc[i] = (uint16_t)(round_pack2<T>(dc, 0.f) & 0xffffu);
+    out_mul[i] = (uint16_t)(round_pack2<T>(m, 0.f) & 0xffffu);
+    out_mul_ok[i] = unit_mul_refused(nr, bad) ? 0 : 1;
+  }
+}
+
+hipError_t launch_debug_unit_div(int dtype, const uint16_t* x, const uint16_t* nrm, uint16_t* out_div, uint16_t* out_divc, uint16_t* out_mul,
+                                 uint8_t* out_mul_ok, int64_t n, hipStream_t st) {
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  if (dtype == 0) hipLaunchKernelGGL(debug_unit_div_kernel<BF16>, dim3(blocks), dim3(256), 0, st, x, nrm, out_div, out_divc, out_mul, out_mul_ok, n);
+  else hipLaunchKernelGGL(debug_unit_div_kernel<F16>, dim3(blocks), dim3(256), 0, st, x, nrm, out_div, out_divc, out_mul, out_mul_ok, n);
+  return hipGetLastError();
+}
+
 size_t merge_max_seq() { return 49152u * 8u; }    // the scatter kernel's position bitmap (one bit per position): 48 KB of dynamic LDS
 
 hipError_t launch_merge(int dtype, const MergeParams& p, hipStream_t st) {
   // the union bitmap and, directly behind it, the per-head flags of the targets kernel
   hipError_t e = hipMemsetAsync(p.mask, 0, (size_t)(reinterpret_cast<char*>(p.kept_bad) - reinterpret_cast<char*>(p.mask)) + (size_t)p.B * p.H * 4, st);
   if (e != hipSuccess) return e;
+#ifdef PKV_DEBUG
+  memset(g_merge_route, 0, sizeof(g_merge_route));
+  g_merge_flags = reinterpret_cast<const unsigned int*>(p.ndrop) + 1;     // the spare word behind ndrop: one bit per data-dependent path
+  e = hipMemsetAsync(const_cast<unsigned int*>(g_merge_flags), 0, 4, st);
+  if (e != hipSuccess) return e;
+#endif
+  PKV_MERGE_ROUTE(MR_NTP, p.ntp);
   const int64_t total = (int64_t)p.B * p.H * p.k;
   const int mb = (int)std::min<int64_t>((total + 255) / 256, 1024);
   hipLaunchKernelGGL(merge_mark_kernel, dim3(mb), dim3(256), 0, st, p);
   static const int droplist2 = merge_env("PKV_MERGE_DROPLIST2", 1);
+  PKV_MERGE_ROUTE(MR_DROPLIST, droplist2 ? 2 : 1); PKV_MERGE_ROUTE(MR_DROP_GRID, droplist2 ? (p.S + MD_SLICE - 1) / MD_SLICE : 1);
   if (droplist2) hipLaunchKernelGGL(merge_droplist2_kernel, dim3((p.S + MD_SLICE - 1) / MD_SLICE), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(merge_droplist_kernel, dim3(1), dim3(1024), 0, st, p);
   if (dtype == 2) return p.D == 64 ? launch_merge_f32_t<4>(p, st) : (p.D == 256 ? launch_merge_f32_t<16>(p, st) : launch_merge_f32_t<8>(p, st));

@@ -444,7 +444,8 @@ def test_merge_cluster_unexpanded_gqa_equals_expanded(P):
 def test_merge_head_sizes_64_and_256(P, D, dt):
     """The LOOK-M merge at head sizes 64 and 256 (kernels templated on the MFMA k-steps D / 32): lattice inputs (norms and dot
     products exact in fp32 in any order) -> bit-identical to oracle.merge_kv, incl. un-expanded GQA K/V, a [B,S,H,D] view,
-    more kept rows than one LDS tile of the pivot kernel (k + w = 208 > 144 / 72) and a group of more than 256 rows."""
+    more kept rows than one LDS tile of the pivot kernel (k + w = 208 > 144 / 80; the tile boundaries themselves, 144 / 145 and
+    80 / 81 kept rows, are cases of tests/merge_routes.py) and a group of more than 256 rows."""
     B, Hk, g, S, w, k = 2, 2, 2, 2203, 8, 200
     H = Hk * g
     _, K, V = make_qkv(B, H, S, D, dt, "lattice", 7600 + D)
