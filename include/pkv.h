@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 203 /* 0.2.3: + pkv_debug_merge_route, pkv_debug_unit_div; no layout change.
+#define PKV_VERSION 204 /* 0.2.4: + pkv_l2norm_workspace_bytes, pkv_compress_l2norm, pkv_debug_sqrt, PKV_K_L2NORM; no struct layout change,
+                           but PKV_K_COUNT grows from 8 to 9: pkv_prof_read now writes 9 entries, so a host built against 203
+                           with arrays of 8 must check pkv_version() (or be rebuilt) before it reads the profile.
+                           0.2.3: + pkv_debug_merge_route, pkv_debug_unit_div; no layout change.
                            0.2.2: + pkv_debug_score_route; no layout change.
                            0.2.1: + pkv_runtime_reset, pkv_debug_scale_multiplier; pkv_ada_budget_rows validates its host
                            mirror (8-byte aligned uint64 [H], host_seq >= 0) like pkv_ada_select; no layout change.  0.2.0: pkv_desc starts with struct_size (the struct can grow without breaking hosts built against an
@@ -51,7 +54,7 @@ enum pkv_status {
 };
 
 /* PKV_F32: pkv_score_window, pkv_score_h2o, pkv_topk(_ws), pkv_gather_compact, pkv_gather_streaming, pkv_gather_flat,
- * pkv_compress, pkv_compress_h2o, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
+ * pkv_compress, pkv_compress_h2o, pkv_compress_l2norm, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
  * pkv_update_flatten_view, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
  * pkv_ada_budget_topm, pkv_ada_adaptive_lists, pkv_ada_select) answers PKV_ERR_DTYPE / PKV_ERR_UNSUPPORTED. */
 enum pkv_dtype { PKV_BF16 = 0, PKV_F16 = 1, PKV_F32 = 2 };
@@ -153,6 +156,27 @@ PKV_API int pkv_compress(const pkv_desc* d, const void* q, const void* k, const 
 /* Fused update_kv for H2O (pyramidkv_utils.py:533-575). */
 PKV_API int pkv_compress_h2o(const pkv_desc* d, const void* q, const void* k, const void* v, void* k_out,
                      void* v_out, int32_t* idx_out, void* ws, size_t ws_bytes, pkv_stream_t stream);
+
+/* Fused update_kv for L2Norm (pyramidkv_utils.py:405-429, L2NormCluster): keep the d->topk keys of SMALLEST L2 norm, in
+ * (norm ascending, index ascending) order; no query, no observation window, no pooling.  Norm scan (:419) -> the canonical
+ * top-k on the negated norms (:420) -> gather (:423-427), on `stream`.
+ *   norm = fp32 sum of squares -> correctly rounded fp32 sqrt -> ONE round-to-nearest-even to d->dtype (what torch.norm
+ *   gives up to the order of the fp32 sum).  Equal norms are kept lowest index first (`argsort` leaves their order to the
+ *   backend).  +inf norms sort last, by index; a NaN norm is ordered with them.
+ * d->window must be 0 (PKV_ERR_SHAPE otherwise; every other entry point keeps rejecting window < 1); d->topk = cap with
+ * 1 <= cap <= S (cap == S returns the full permutation); q_stride, pool_kind, pool_kernel, reduce and scale_mode are
+ * ignored; the order is always canonical.  d->kv_group = g: k, v have H/g heads; norms and selection run ONCE per KV head
+ * and every query head of a group receives its rows.
+ *   k_out, v_out: contiguous [B,H,cap,D] (no window rows are appended).
+ *   idx_out:      int32 [B*H][cap], may be NULL.
+ *   norm_out:     d->dtype [B*(H/g)][S] contiguous, the norms themselves; may be NULL; 16-byte aligned.
+ *   ws:           pkv_l2norm_workspace_bytes(d), 16-B aligned (0 = the descriptor is not one this entry point takes).
+ * Limits = those of the selection: one workgroup up to S = 57 344 with cap <= 16 384; longer rows in segments with
+ * cap <= 4096; a complete sort of the row for larger cap up to S = 32 768 (16-bit dtypes); PKV_F32: cap <= 4096.
+ * PKV_ERR_UNSUPPORTED beyond. */
+PKV_API size_t pkv_l2norm_workspace_bytes(const pkv_desc* d);
+PKV_API int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k_out, void* v_out, int32_t* idx_out,
+                        void* norm_out, void* ws, size_t ws_bytes, pkv_stream_t stream);
 
 /* Selection only: the front half of pkv_compress / pkv_compress_h2o (score -> top-k), idx_out int32 [B*H][d->topk].
  * What a caller needs when something other than the plain gather follows (the merge below).  ws: pkv_workspace_bytes(d). */
@@ -281,10 +305,10 @@ PKV_API int pkv_last_nccl_error(void); /* ncclResult_t of the last PKV_ERR_COLLE
 /* ---- per-kernel device timing (hipEvent pairs on `stream`), used by bench.py ---- */
 enum pkv_kernel_id {
   PKV_K_LOGITS = 0, PKV_K_FINALIZE = 1, PKV_K_TOPK = 2, PKV_K_GATHER = 3, PKV_K_H2O_STATS = 4,
-  PKV_K_H2O_COLSUM = 5, PKV_K_SORT = 6, PKV_K_BUDGET = 7, PKV_K_COUNT = 8
+  PKV_K_H2O_COLSUM = 5, PKV_K_SORT = 6, PKV_K_BUDGET = 7, PKV_K_L2NORM = 8, PKV_K_COUNT = 9
 };
 PKV_API int pkv_prof_enable(int on);                                   /* returns previous state */
-PKV_API int pkv_prof_read(double* ms_sum, int64_t* launches, int reset); /* arrays of PKV_K_COUNT; syncs events */
+PKV_API int pkv_prof_read(double* ms_sum, int64_t* launches, int reset); /* arrays of PKV_K_COUNT (9 since 0.2.4); syncs events */
 
 /* ---- debug / test hooks (not part of the drop-in surface) ----
  * The trace hooks and the PKV_LOGITS_ABLATE measurement knob exist only in the -DPKV_DEBUG build (libpkv_debug.so,
@@ -320,6 +344,9 @@ PKV_API int pkv_debug_merge_route(int32_t* out, int n);
  * that the suite checks the shipped code, not a copy.  Nothing on the product path launches them (~2 KB of code). */
 PKV_API int pkv_debug_exp(const float* in, float* out, int64_t n, pkv_stream_t stream);
 PKV_API int pkv_debug_round(int32_t dtype, const float* in, void* out, int64_t n, pkv_stream_t stream);
+/* ... and the fp32 square root the key-norm scan of pkv_compress_l2norm inlines (correctly rounded: tests/test_gpu_l2norm.py
+ * compares it with the float64 square root, so a build flag that trades it for the bare hardware instruction fails there). */
+PKV_API int pkv_debug_sqrt(const float* in, float* out, int64_t n, pkv_stream_t stream);
 /* Test hook of the RELEASE library: "element / norm, rounded to the model dtype" of the LOOK-M merge in the three forms the merge
  * kernels inline (pkv_common.hpp: unit_div, unit_div_const, unit_mul), element-wise over n (x, norm) pairs of 16-bit values
  * (device pointers): out_div / out_divc / out_mul receive the rounded results, out_mul_ok[i] = 1 where merge_pivot2_kernel's

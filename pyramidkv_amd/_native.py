@@ -19,10 +19,10 @@ POOL = {None: 0, "none": 0, "avgpool": 1, "maxpool": 2}
 REDUCE = {"sum": 0, "mean": 1}
 SCALE = {"div": 0, "rcp": 1}
 TIE = {"canonical": 0, "aten_rocm": 1}
-KERNEL_NAMES = ["logits", "finalize", "topk", "gather", "h2o_stats", "h2o_colsum", "sort", "budget"]
+KERNEL_NAMES = ["logits", "finalize", "topk", "gather", "h2o_stats", "h2o_colsum", "sort", "budget", "l2norm"]
 
 
-PKV_VERSION = 203            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
+PKV_VERSION = 204            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
 
 
 class PkvDesc(C.Structure):
@@ -78,6 +78,8 @@ def _load():
         "pkv_compress": (C.c_int, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "pkv_compress_h2o": (C.c_int, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "pkv_select": (C.c_int, [dp, vp, vp, i32, vp, vp, sz, vp]),
+        "pkv_l2norm_workspace_bytes": (sz, [dp]),
+        "pkv_compress_l2norm": (C.c_int, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
         "pkv_merge_workspace_bytes": (sz, [dp]),
         "pkv_merge_compact": (C.c_int, [dp, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
         "pkv_sort_rows": (C.c_int, [i32, i32, i32, vp, i64, vp, vp, vp]),
@@ -99,6 +101,7 @@ def _load():
         "pkv_debug_exp": (C.c_int, [vp, vp, i64, vp]),
         "pkv_debug_unit_div": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i64, vp]),
         "pkv_debug_round": (C.c_int, [i32, vp, vp, i64, vp]),
+        "pkv_debug_sqrt": (C.c_int, [vp, vp, i64, vp]),
         "pkv_debug_scale_multiplier": (C.c_float, [i32, i32, i32]),
         "pkv_prof_enable": (C.c_int, [C.c_int]),
         "pkv_prof_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),

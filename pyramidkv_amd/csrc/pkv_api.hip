@@ -331,6 +331,16 @@ bool topk_fits(int L, int k) {
   return lds <= 160 * 1024 && 16 * (size_t)Lw <= 65536;
 }
 
+// the long-row path of do_topk: the top-k of every TK_SEG segment, then one workgroup over the nseg*k winners.  The one
+// statement of what that path can take: do_topk asks it, and so does an entry point that must refuse before its first launch.
+// For do_topk it restates what its two launch() calls refuse (segments of TK_SEG keys, then nseg*k candidates): the same
+// rows get PKV_ERR_UNSUPPORTED, now before the first launch instead of after it; no route changes.
+bool topk_long_fits(int rows, int L, int k) {
+  if (k > TK_SEG || !topk_fits(TK_SEG, k)) return false;
+  const int64_t nseg = ((int64_t)L + TK_SEG - 1) / TK_SEG, cand = nseg * k;
+  return cand <= 0x7fffffff && topk_fits((int)cand, k) && rows * nseg <= 0x7fffffff;
+}
+
 // scratch of the long-row path: segment winners [rows][nseg*k] int32, their scores, positions of the final winners
 size_t topk_tmp_bytes(int rows, int L, int k) {
   if (L < 1 || k < 1 || rows < 1 || topk_fits(L, k)) return 0;
@@ -371,10 +381,9 @@ int do_topk(int dtype, int rows, int L, int k, const void* scores, int64_t strid
   // the nseg*k winners.  The candidate list is segment-major, so position order == index order among equal scores and
   // the second selection reproduces (value desc, index asc) of the whole row.
   const size_t need = topk_tmp_bytes(rows, L, k);
-  if (!tmp || tmp_bytes < need || kpr || k > TK_SEG || (reinterpret_cast<uintptr_t>(tmp) & 15)) return PKV_ERR_UNSUPPORTED;
+  if (!tmp || tmp_bytes < need || kpr || (reinterpret_cast<uintptr_t>(tmp) & 15) || !topk_long_fits(rows, L, k)) return PKV_ERR_UNSUPPORTED;
   const int nseg = (L + TK_SEG - 1) / TK_SEG;
   const int64_t cand = (int64_t)nseg * k, cstride = (int64_t)align_up((size_t)cand, 8);
-  if (!topk_fits((int)cand, k) || (int64_t)rows * nseg > 0x7fffffff) return PKV_ERR_UNSUPPORTED;
   char* t8 = static_cast<char*>(tmp);
   int32_t* cand_idx = reinterpret_cast<int32_t*>(t8);
   void* cand_score = t8 + align_up((size_t)rows * cand * 4, 256);
@@ -579,6 +588,106 @@ int pkv_select(const pkv_desc* d, const void* q, const void* k, int32_t h2o, int
     if (e != hipSuccess) return hip_fail(e);
   }
   return PKV_OK;
+}
+
+// ---- L2Norm (pyramidkv_utils.py:405-429): norm scan -> canonical top-k of the negated norms -> gather with w = 0 ----
+namespace {
+struct L2Ws {
+  int Lp, rows_kv;
+  bool sort;                 // cap beyond one top-k workgroup on a row the sort kernel holds: the complete canonical order
+  size_t off_scores, off_sel, off_idx, off_tk, tk_bytes, total;
+};
+
+// window == 0 is this entry point's alone (check_desc keeps rejecting it everywhere else)
+int check_l2norm_desc(const pkv_desc* d) {
+  if (d->dtype != PKV_BF16 && d->dtype != PKV_F16 && d->dtype != PKV_F32) return PKV_ERR_DTYPE;
+  if (d->D != 64 && d->D != 128 && d->D != 256) return PKV_ERR_SHAPE;
+  if (d->B < 1 || d->H < 1 || d->S < 1) return PKV_ERR_SHAPE;
+  if (d->kv_group < 1 || d->H % d->kv_group) return PKV_ERR_SHAPE;
+  if (d->window != 0) return PKV_ERR_SHAPE;
+  if (d->topk < 1 || d->topk > d->S) return PKV_ERR_SHAPE;
+  if (d->tie_order != PKV_TIE_CANONICAL && d->tie_order != PKV_TIE_ATEN_ROCM) return PKV_ERR_SHAPE;
+  const int64_t amask = d->dtype == PKV_F32 ? 3 : 7;
+  for (int i = 0; i < 3; ++i)
+    if ((d->k_stride[i] & amask) || (d->v_stride[i] & amask)) return PKV_ERR_ALIGN;
+  if ((int64_t)d->B * d->H > 65535) return PKV_ERR_UNSUPPORTED;
+  if (d->dtype == PKV_F32 && d->topk > topk_f32_max_k()) return PKV_ERR_UNSUPPORTED;
+  return PKV_OK;
+}
+
+L2Ws l2norm_ws(const pkv_desc* d) {
+  L2Ws w;
+  const size_t es = d->dtype == PKV_F32 ? 4 : 2;
+  w.rows_kv = d->B * (d->H / d->kv_group);
+  w.Lp = (int)align_up((size_t)d->S, 8);
+  w.sort = d->dtype != PKV_F32 && d->topk > 4096 && d->S <= 32768 && !topk_fits(d->S, d->topk);
+  size_t o = 0;
+  w.off_scores = o; o = align_up(o + (size_t)w.rows_kv * w.Lp * es, 256);
+  w.off_sel = o;    o = align_up(o + (size_t)w.rows_kv * (w.sort ? d->S : d->topk) * 4, 256);     // one index row per KV head
+  w.off_idx = o;    o = align_up(o + (size_t)d->B * d->H * d->topk * 4, 256);                      // one per query head (idx_out == NULL)
+  w.tk_bytes = w.sort ? 0 : topk_tmp_bytes(w.rows_kv, d->S, d->topk);
+  w.off_tk = o;     o = align_up(o + w.tk_bytes, 256);
+  w.total = o;
+  return w;
+}
+}  // namespace
+
+size_t pkv_l2norm_workspace_bytes(const pkv_desc* d) {
+  PKV_LOAD_DESC(d, 0);
+  if (check_l2norm_desc(d)) return 0;
+  return l2norm_ws(d).total;
+}
+
+int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k_out, void* v_out, int32_t* idx_out,
+                        void* norm_out, void* ws, size_t ws_bytes, pkv_stream_t stream) {
+  PKV_LOAD_DESC(d, rc_ld);
+  int rc = check_l2norm_desc(d);
+  if (rc) return rc;
+  if (!k || !v || !k_out || !v_out || !ws) return PKV_ERR_NULL;
+  if (misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out) || misaligned(ws) || misaligned(norm_out))
+    return PKV_ERR_ALIGN;
+  const L2Ws W = l2norm_ws(d);
+  const int S = d->S, cap = d->topk, G = d->kv_group, BH = d->B * d->H;
+  // do_topk's own question, asked before anything is launched (fp32 budgets were bounded by check_l2norm_desc)
+  if (d->dtype != PKV_F32 && !W.sort && !topk_fits(S, cap) && !topk_long_fits(W.rows_kv, S, cap)) return PKV_ERR_UNSUPPORTED;
+  if (ws_bytes < W.total) return PKV_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  void* scores = w + W.off_scores;
+  {
+    L2NormParams np;
+    np.kptr = k; np.neg_out = scores; np.norm_out = norm_out;
+    np.B = d->B; np.Hkv = d->H / G; np.S = S; np.D = d->D; np.Lp = W.Lp;
+    np.ks_b = d->k_stride[0]; np.ks_h = d->k_stride[1]; np.ks_s = d->k_stride[2];
+    np.nblk = 0; np.norm_vec = 0;
+    ProfScope ps(PKV_K_L2NORM, st, true);
+    hipError_t e = launch_l2norm(d->dtype, np, st);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  // the selection: one row per KV HEAD (the policy ignores Q: all g query heads of a group keep the same rows)
+  int32_t* fin = idx_out ? idx_out : reinterpret_cast<int32_t*>(w + W.off_idx);      // [B*H][cap], what the gather reads
+  const bool direct = G == 1 && !W.sort;                                             // the selection writes `fin` itself
+  int32_t* sel = direct ? fin : reinterpret_cast<int32_t*>(w + W.off_sel);
+  int64_t sel_stride = cap;
+  if (W.sort) {
+    SortParams sp;
+    sp.scores = scores; sp.scores_stride = W.Lp; sp.L = S; sp.n = (S + 7) & ~7;
+    sp.sorted_idx = sel; sp.sorted_val = nullptr; sp.trace = g_topk_trace;
+    sel_stride = S;
+    ProfScope ps(PKV_K_SORT, st);
+    hipError_t e = launch_sort_rows(d->dtype, W.rows_kv, sp, st);
+    if (e != hipSuccess) return hip_fail(e);
+  } else {
+    rc = do_topk(d->dtype, W.rows_kv, S, cap, scores, W.Lp, nullptr, sel, cap, st, nullptr, 0, w + W.off_tk, W.tk_bytes);
+    if (rc) return rc;
+  }
+  if (!direct) {
+    hipError_t e = launch_idx_expand(sel, sel_stride, fin, BH, cap, G, st);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  GatherParams g = make_gather(d, k, v, k_out, v_out);      // w = 0: L = S, no window rows behind the selected ones
+  g.idx = fin; g.idx_stride = cap;
+  return do_gather(g, cap, st);
 }
 
 namespace {
@@ -883,6 +992,13 @@ float pkv_debug_scale_multiplier(int32_t dtype, int32_t D, int32_t scale_mode) {
 
 int pkv_debug_exp(const float* in, float* out, int64_t n, pkv_stream_t stream) {
   hipError_t e = launch_debug_exp(in, out, n, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? PKV_OK : hip_fail(e);
+}
+
+int pkv_debug_sqrt(const float* in, float* out, int64_t n, pkv_stream_t stream) {
+  if (!in || !out) return PKV_ERR_NULL;
+  if (n < 1) return PKV_ERR_SHAPE;
+  hipError_t e = launch_debug_sqrt(in, out, n, static_cast<hipStream_t>(stream));
   return e == hipSuccess ? PKV_OK : hip_fail(e);
 }
 

@@ -265,6 +265,18 @@ struct FlattenParams {
   int H, row_bytes;
 };
 
+struct L2NormParams {        // key-norm scan of the L2Norm policy (pkv_l2norm.hip)
+  const void* kptr;          // [B, Hkv, S, D], element strides below
+  void* neg_out;             // [B*Hkv][Lp] model dtype: -norm (+0 for a zero norm, -inf for a NaN norm); Lp % 8 == 0, Lp >= S.
+                             // The padding S..Lp-1 is NOT neutral: it holds copies of row S-1's value, so whatever reads
+                             // the row must mask by L = S (topk_kernel, topk_f32_kernel and sort_rows_kernel all do)
+  void* norm_out;            // [B*Hkv][S] model dtype: the norms themselves, or null
+  int B, Hkv, S, D, Lp;
+  int64_t ks_b, ks_h, ks_s;
+  int nblk;                  // row blocks per head (set by launch_l2norm)
+  int norm_vec;              // norm_out takes 16-byte stores (set by launch_l2norm)
+};
+
 struct H2OParams {
   const void* q;
   const void* k;
@@ -308,6 +320,10 @@ hipError_t launch_ada_metadata(int H, int w, const int32_t* cap, int32_t* head_l
 hipError_t launch_flatten(const FlattenParams& p, hipStream_t st);
 hipError_t launch_merge(int dtype, const MergeParams& p, hipStream_t st);
 size_t merge_max_seq();      // longest sequence the merge takes (LDS bitmap of the scatter kernel)
+hipError_t launch_l2norm(int dtype, const L2NormParams& p, hipStream_t st);
+// dst [BH][n] = src row bh / G (stride src_stride), entries 0..n-1
+hipError_t launch_idx_expand(const int32_t* src, int64_t src_stride, int32_t* dst, int BH, int n, int G, hipStream_t st);
+hipError_t launch_debug_sqrt(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_exp(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_round(int dtype, const float* in, uint16_t* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_unit_div(int dtype, const uint16_t* x, const uint16_t* nrm, uint16_t* out_div, uint16_t* out_divc, uint16_t* out_mul,

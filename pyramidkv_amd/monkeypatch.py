@@ -12,7 +12,7 @@ contract of ``llama_model.py:157-172`` on top of the transformers-5 attention mo
     cache at decode.
 
 As in the reference the cache stores all H (query) heads, because K/V are expanded before ``update_kv``.
-``pyramidkv``, ``snapkv``, ``h2o``, ``streamingllm`` use the model's own cache object.  ``adakv`` / ``headkv``
+``pyramidkv``, ``snapkv``, ``h2o``, ``streamingllm``, ``l2norm`` use the model's own cache object.  ``adakv`` / ``headkv``
 (reference llama_model.py:2236-2391 / :2393-2540) keep a FLAT per-head var-len cache: pass a
 ``pyramidkv_amd.DynamicCacheSplitHeadFlatten()`` as ``past_key_values`` (batch 1, as the reference); the decode step
 appends through ``pkv_update_flatten_view`` and attends per head over its own rows - the reference calls
@@ -34,6 +34,7 @@ _METHODS: Dict[str, tuple] = {
     "snapkv": ("init_snapkv", False),
     "h2o": ("init_H2O", False),
     "streamingllm": ("init_StreamingLLM", False),
+    "l2norm": ("init_l2norm_native", False),      # reference monkeypatch.py:60-64,124-128; init_l2norm itself is a pinned placeholder
 }
 _FLAT_METHODS: Dict[str, str] = {"adakv": "init_adakv", "headkv": "init_headkv"}
 # the module whose init_* functions build the clusters; tests swap in an oracle-backed stand-in on CPU

@@ -280,6 +280,43 @@ def compress(q, k, v, window: int, topk_k: int, pooling, kernel_size: int, scale
     return (ko, vo, idx) if return_indices else (ko, vo)
 
 
+def compress_l2norm(k, v, cap: int, kv_group: int = 1, idx_out: Optional[torch.Tensor] = None, return_indices: bool = False,
+                    return_norms: bool = False):
+    """L2Norm (pyramidkv_utils.py:405-429) in one C call: key norms -> the ``cap`` keys of smallest norm in (norm ascending,
+    index ascending) order -> gather.  k, v: [B, H/kv_group, S, D]; norms and selection run once per KV head and every
+    query head of a group receives its rows.  Returns (K_c, V_c) [B, H, cap, D], then int32 indices [B, H, cap] with
+    ``return_indices`` / ``idx_out`` (contiguous int32, B*H*cap elements), then the norms [B, H/kv_group, S] in the model dtype
+    with ``return_norms``."""
+    _require_gpu(k, v)
+    k, v = _rowmajor(k), _rowmajor(v)
+    B, Hk, S, D = k.shape
+    H = Hk * kv_group
+    with _DeviceGuard(k.device):
+        d = make_desc(None, k, v, 0, topk=cap, kv_group=kv_group, num_heads=H)
+        nb = N.lib.pkv_l2norm_workspace_bytes(d)
+        ws, st = _workspace_and_stream(max(nb, 1), k.device)        # nb == 0: the call below names what is wrong with the descriptor
+        ko = torch.empty(B, H, max(cap, 0), D, dtype=k.dtype, device=k.device)
+        vo = torch.empty_like(ko)
+        if idx_out is not None:
+            if idx_out.dtype != torch.int32 or not idx_out.is_contiguous() or idx_out.numel() != B * H * cap:
+                raise ValueError("idx_out must be a contiguous int32 tensor of B*H*k elements")
+            idx, return_indices = idx_out, True
+        else:
+            idx = torch.empty(B, H, cap, dtype=torch.int32, device=k.device) if return_indices else None
+        norms = torch.empty(B, Hk, S, dtype=k.dtype, device=k.device) if return_norms else None
+        rc = N.lib.pkv_compress_l2norm(d, k.data_ptr(), v.data_ptr(), ko.data_ptr(), vo.data_ptr(),
+                                       idx.data_ptr() if idx is not None else None,
+                                       norms.data_ptr() if norms is not None else None, ws.data_ptr(), ws.numel(), st)
+        if rc:
+            N.check(rc, "pkv_compress_l2norm")
+    out = (ko, vo)
+    if return_indices:
+        out += (idx,)
+    if return_norms:
+        out += (norms,)
+    return out
+
+
 # ---- prepared calls (round 5): everything of one update_kv that does not change from call to call ----------------------
 # At S <= 8192 one dense update_kv is bound by the HOST's time to issue it (bench.py `sweep[].host_us`).  A cluster therefore
 # keeps, per (shapes, strides, dtype, device, budget, knobs), the filled descriptor, its byref object, the scratch size and the

@@ -291,6 +291,38 @@ class StreamingLLMKVCluster:
         return _repeat_kv(kc, g), _repeat_kv(vc, g)       # every head of a group keeps the same tokens
 
 
+class L2NormCluster:
+    """reference pyramidkv_utils.py:394-429: keep the ``max_capacity_prompt`` keys of smallest L2 norm, in ascending-norm
+    order (equal norms: lowest index first).  No query, no observation window: every query head of a GQA group keeps the
+    same rows, so norms and selection run once per KV head (un-expanded K/V, or the de-duplicated view under
+    config.gqa_dedup)."""
+
+    accepts_unexpanded_kv = True
+    index_out = None                  # as _WindowPolicy.index_out: contiguous int32 [B, H, cap], written when the call selects
+
+    def __init__(self, max_capacity_prompt=256 + 64, layer_idx=0, skip_layers=None):
+        self.reset(max_capacity_prompt, layer_idx, skip_layers)
+
+    def reset(self, max_capacity_prompt=256 + 64, layer_idx=0, skip_layers=None):
+        self.max_capacity_prompt = max_capacity_prompt
+        self.layer_idx = layer_idx
+        self.skip_layers = [] if skip_layers is None else skip_layers             # :395 shares one mutable default list
+
+    def update_kv(self, key_states, query_states, value_states, attention_mask, num_key_value_groups):
+        assert key_states.shape[-2] == query_states.shape[-2]                       # :408
+        q_len = query_states.shape[-2]
+        if q_len < self.max_capacity_prompt:                                        # :413
+            return _WindowPolicy._passthrough(key_states, query_states, value_states)
+        if self.layer_idx in self.skip_layers:                                      # :415
+            return _WindowPolicy._passthrough(key_states, query_states, value_states)
+        g = _unexpanded_group(key_states, query_states)
+        if g == 1:
+            g = _kv_group(num_key_value_groups, query_states.shape[1])
+            key_states, value_states = _dedup_view(key_states, g), _dedup_view(value_states, g)
+        return ops.compress_l2norm(key_states, value_states, self.max_capacity_prompt, kv_group=g,   # :419-427
+                                   idx_out=self.index_out)[:2]
+
+
 _PINNED = threading.local()      # per host thread: two threads reading capacities back never share a staging buffer
 
 
@@ -855,16 +887,31 @@ def init_headkv(self):
             head_capacity=self.config.head_capacity)
 
 
+def init_l2norm_native(self):
+    """reference :954-968 (init_l2norm: same defaults, cluster rebuilt on every call, as there).  ``init_l2norm`` itself stays
+    the placeholder below - a test pins that it raises - so ``replace_llama("l2norm")`` names this factory."""
+    if not hasattr(self, "kv_cluster"):
+        _default(self.config, 'max_capacity_prompt', 4096)
+        _default(self.config, 'layer_idx', 0)
+        _default(self.config, 'skip_layers', [0, 1])
+    _rebuilt(self, L2NormCluster(max_capacity_prompt=self.config.max_capacity_prompt, layer_idx=self.layer_idx,
+                                 skip_layers=self.config.skip_layers))
+
+
 def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
     """reference pyramidkv_utils.py:108-117 (same name and behaviour: n_rep == 1 returns the input object)."""
     return _repeat_kv(hidden_states, n_rep)
 
 
-def _out_of_scope(name, where):
+def _out_of_scope(name, where, instead=None):
     def init(self, *args, **kwargs):
+        if instead is not None:
+            raise NotImplementedError(
+                f"{name} (reference pyramidkv_utils.py:{where}) is a placeholder in pyramidkv_amd: the working factory is "
+                f"{instead}(self) (same defaults; replace_llama / replace_mistral use it)")
         raise NotImplementedError(
             f"{name} (reference pyramidkv_utils.py:{where}) is outside the scope of pyramidkv_amd (SURVEY.md section 2: "
-            "CAM / L2Norm / ThinK are not on the update_kv hot path); the name exists so that the reference's "
+            "CAM / ThinK are not on the update_kv hot path); the name exists so that the reference's "
             "llama_model.py / mistral_model.py import this module unchanged")
     init.__name__ = name
     init.__doc__ = f"Placeholder for the reference's {name} (:{where}); raises NotImplementedError when called."
@@ -873,7 +920,7 @@ def _out_of_scope(name, where):
 
 # llama_model.py:16, llama_model_think.py:16 and mistral_model.py:19 import these three from this module.
 init_CAM = _out_of_scope("init_CAM", "970-988")
-init_l2norm = _out_of_scope("init_l2norm", "954-968")
+init_l2norm = _out_of_scope("init_l2norm", "954-968", instead="init_l2norm_native")
 init_think = _out_of_scope("init_think", "926-952")
 
 
