@@ -51,7 +51,12 @@ int ada_fused() { static int t = env_int("PKV_ADA_FUSED", 1); return t; }     //
 int gather_rpt() { static int t = env_int("PKV_GATHER_RPT", 0); return t; }   // 0 = by size (launch_gather)
 int gather_xcd() { static int t = env_int("PKV_GATHER_XCD", 0); return t; }
 
-inline int hip_fail(hipError_t e) { g_last_hip = (int)e; return PKV_ERR_HIP; }
+// a HIP call's result as a pkv_status; the error itself is kept for pkv_last_hip_error()
+inline int hip_rc(hipError_t e) {
+  if (e == hipSuccess) return PKV_OK;
+  g_last_hip = (int)e;
+  return PKV_ERR_HIP;
+}
 
 // the constant the 16-bit kernels multiply a logit by instead of dividing it by fp32(sqrt(head_dim)) - pkv_common.hpp scale_logit
 float scale_multiplier(int dtype, int D, int scale_mode) {
@@ -124,33 +129,44 @@ int load_desc(const pkv_desc* in, pkv_desc* out) {
     if (rc_ld) return on_fail;                                      \
   }                                                                 \
   d = &d##_own
-// f32_ok: the entry point has an fp32 path (window scores, top-k, dense / streaming gather); every other one answers
-// PKV_ERR_UNSUPPORTED for fp32 tensors
-int check_desc(const pkv_desc* d, bool need_topk, bool scoring = true, bool f32_ok = false) {
+// What an entry point asks of its descriptor.  The ORDER of the checks below decides which error a descriptor with several
+// defects gets: tests/golden/abi_status_table.json is the record of it.
+enum DescNeed : unsigned {
+  NEED_TOPK = 1,   // d->topk is read: 1 <= topk <= S - window (fp32: up to the radix select's cap)
+  SCORING = 2,     // the K scan runs: window <= 128, kv_group * window <= 256
+  F32_OK = 4,      // the entry point has an fp32 path (window scores, top-k, the gathers, merge); every other one answers
+                   // PKV_ERR_UNSUPPORTED for fp32 tensors
+  L2NORM = 8,      // pkv_compress_l2norm alone: window must be 0 (everywhere else it is >= 1), S >= 1, topk <= S; q strides and
+                   // the pooling fields are not looked at
+};
+int check_desc(const pkv_desc* d, unsigned need) {
+  const bool l2 = need & L2NORM, need_topk = need & NEED_TOPK;
   if (!d) return PKV_ERR_NULL;
   if (d->dtype != PKV_BF16 && d->dtype != PKV_F16 && d->dtype != PKV_F32) return PKV_ERR_DTYPE;
   if (d->D != 64 && d->D != 128 && d->D != 256) return PKV_ERR_SHAPE;
-  if (d->dtype == PKV_F32 && !f32_ok) return PKV_ERR_UNSUPPORTED;
-  if (d->B < 1 || d->H < 1 || d->S < 2) return PKV_ERR_SHAPE;
+  if (d->dtype == PKV_F32 && !(need & F32_OK)) return PKV_ERR_UNSUPPORTED;
+  if (d->B < 1 || d->H < 1 || d->S < (l2 ? 1 : 2)) return PKV_ERR_SHAPE;
   if (d->kv_group < 1 || d->H % d->kv_group) return PKV_ERR_SHAPE;
-  if (d->window < 1 || d->window >= d->S) return PKV_ERR_SHAPE;
-  if (scoring && (d->window > 128 || d->kv_group * d->window > 256)) return PKV_ERR_UNSUPPORTED;
+  if (l2 ? d->window != 0 : d->window < 1 || d->window >= d->S) return PKV_ERR_SHAPE;
+  if ((need & SCORING) && (d->window > 128 || d->kv_group * d->window > 256)) return PKV_ERR_UNSUPPORTED;
   if (need_topk && (d->topk < 1 || d->topk > d->S - d->window)) return PKV_ERR_SHAPE;
-  if (d->pool_kind < 0 || d->pool_kind > 2) return PKV_ERR_SHAPE;
+  if (!l2 && (d->pool_kind < 0 || d->pool_kind > 2)) return PKV_ERR_SHAPE;
   if (d->tie_order != PKV_TIE_CANONICAL && d->tie_order != PKV_TIE_ATEN_ROCM) return PKV_ERR_SHAPE;
-  if (d->pool_kind != PKV_POOL_NONE) {
+  if (!l2 && d->pool_kind != PKV_POOL_NONE) {
     if (d->pool_kernel < 1 || !(d->pool_kernel & 1)) return PKV_ERR_SHAPE;
     if (d->pool_kernel > 17) return PKV_ERR_UNSUPPORTED;
   }
   const int64_t amask = d->dtype == PKV_F32 ? 3 : 7;                       // rows start on 16-byte boundaries
   for (int i = 0; i < 3; ++i)
-    if ((d->q_stride[i] & amask) || (d->k_stride[i] & amask) || (d->v_stride[i] & amask)) return PKV_ERR_ALIGN;
+    if ((!l2 && (d->q_stride[i] & amask)) || (d->k_stride[i] & amask) || (d->v_stride[i] & amask)) return PKV_ERR_ALIGN;
   if ((int64_t)d->B * d->H > 65535) return PKV_ERR_UNSUPPORTED;
   if (d->dtype == PKV_F32 && need_topk && d->topk > topk_f32_max_k()) return PKV_ERR_UNSUPPORTED;
   return PKV_OK;
 }
 
 size_t topk_tmp_bytes(int rows, int L, int k);
+// scratch of the budget entry points: 1024 B of ratios + two 256-bin int32 tables per head (fp32 rows: four, + 4 words per head)
+inline size_t ada_ws_bytes(int H, bool fp32) { return fp32 ? 1024 + (size_t)4 * H * 256 * 4 + (size_t)4 * H * 4 : 1024 + (size_t)2 * H * 256 * 4; }
 
 struct WsLayout {
   int Sp, nT, Lp;
@@ -173,85 +189,84 @@ WsLayout ws_layout(const pkv_desc* d) {
   w.off_cmax = o;    o = align_up(o + (size_t)d->B * d->H * (w.Lp / 8) * 2, 256);
   w.tk_bytes = d->topk > 0 ? topk_tmp_bytes(d->B * d->H, d->S - d->window, d->topk) : 0;      // long-row top-k scratch (0 up to 57 344 keys)
   w.off_tk = o;      o = align_up(o + w.tk_bytes, 256);
-  w.off_ada = o;     o = align_up(o + 1024 + (size_t)2 * d->H * 256 * 4, 256);                 // Ada-SnapKV budget scratch (pkv_ada_select)
+  w.off_ada = o;     o = align_up(o + ada_ws_bytes(d->H, false), 256);                          // Ada-SnapKV budget scratch (pkv_ada_select)
   w.off_ada_list = o; o = align_up(o + (size_t)d->H * align_up((size_t)(d->topk > 0 ? d->topk : 1), 8) * 2, 256);   // looked-up top-M lists
   w.off_rowstat = o; o = align_up(o + (size_t)d->B * d->H * d->S * sizeof(float2), 256);   // H2O only: c_row of every query row (fp32 tensors: (max, 1/sum) pairs)
   w.total = o;
   return w;
 }
 
+// stages per workgroup (nst) and workgroups per head group (nT) of logits2_kernel: a pure function of the shape, the CU count
+// and PKV_LOGITS_V2_WGS (tests/score_routes.py restates it).
+struct ScanStages { int nst, nT; };
+ScanStages logits2_stages(int B, int H, int G, int S, int C, int cus, int wgs) {
+  const int sph = (S + 127) / 128;                                          // stages per head group
+  const int64_t total = (int64_t)B * (H / G) * sph;
+  // stages per workgroup.  C <= 8 columns (expanded K/V, window 8): ONE stage per workgroup - measured in round 2 over
+  // {1, 2, 3, 4, 8 stages}: 1 is the fastest at B = 1 (45.1-46.0 us against 45.7-48.6 us for 4 stages in the same
+  // sessions; 2 and 3 stages are the slowest) and at B = 8 (350 vs 353 us): the in-workgroup pipeline only pays when few
+  // workgroups share a CU.  Round 4 tried a chunk-WALKING grid (as many workgroups as the chip holds at once, each walking
+  // chunks blockIdx.x, + gridDim.x, ... with the next chunk's rows in flight): the loop costs 21 registers (one workgroup
+  // per CU less, or spills), C = 8: 44.7 -> 58.7 us at 4 per CU, C = 32: 19.95 -> 19.8 us; and TWO stages of K rows in flight
+  // per workgroup (a second register set: 166 / 204 registers = one workgroup per CU less): C = 8: 44.6 -> 48.4 us, C = 32:
+  // 17.1 -> 21.0 us (19.2 with 4 stages per workgroup).  Both removed (profiles/r04/ab/).
+  // More columns per stage (un-expanded GQA K, C = 32): 4 workgroups per CU with 2..8 stages each
+  // (one stage per workgroup costs +4 us there).  Round 3, after the logits stores moved one stage back (pkv_score.hip):
+  // same ranking - C = 8: 44.3 us at 1 stage, 46.2 / 45.6 / 46.4 / 47.3 at 2 / 4 / 8 / 16; C = 32: 16.8 us at 2 stages
+  // (1024 workgroups), 17.2 at 3, 17.3 at 4, 20.1 at 1 (profiles/r03/ab/defer_stores_ab.txt, one_stage_lds_direct_ab.txt).
+  // Round 4 measured the review's "every finalize workgroup re-merges all partials of its head" (256 per row at one stage per
+  // workgroup): 8 stages per workgroup at B = 8 (32 partials per row) left finalize_kernel at 44.5 us - it is bound by its
+  // ~790 vector instructions per wave, not by those reads - and the K scan at 344 us.  One stage stays.
+  // Round 6: a launch of at most TWO rounds of the chip's 4-per-CU residency (S = 8192 at B = 1: 2048 stages) runs as ONE round of
+  // two-stage workgroups - 14.4 -> 13.5 us there (tools/probes/scan_stages_probe.py); one stage per workgroup stays the
+  // fastest from three rounds up (S = 16384: 25.2 either way, S = 32768: 45.9 against 48-51 us).
+  const int64_t target = wgs > 0 ? wgs
+                       : (C > 8 ? (int64_t)4 * cus : (total > (int64_t)4 * cus && total <= (int64_t)8 * cus ? (int64_t)4 * cus : total));
+  int nst = (int)((total + target - 1) / target);
+  nst = std::max(1, std::min(nst, std::min(sph, 64)));
+  return {nst, (sph + nst - 1) / nst};
+}
+
+// what LogitsParams and H2OParams share: tensors, shape, q / k strides and the logit scale
+template <class P>
+void fill_qk(P& p, const pkv_desc* d, const void* q, const void* k) {
+  p.q = q; p.k = k;
+  p.B = d->B; p.H = d->H; p.S = d->S; p.w = d->window; p.G = d->kv_group; p.D = d->D;
+  p.qs_b = d->q_stride[0]; p.qs_h = d->q_stride[1]; p.qs_s = d->q_stride[2];
+  p.ks_b = d->k_stride[0]; p.ks_h = d->k_stride[1]; p.ks_s = d->k_stride[2];
+  p.scale_mode = d->scale_mode;
+  p.sqrt_d = (float)sqrt((double)d->D);   // math.sqrt(head_dim), cast to the fp32 opmath type
+  p.rcp_sqrt_d = d->dtype == PKV_F32 ? 1.0f / p.sqrt_d : scale_multiplier(d->dtype, d->D, d->scale_mode);
+}
+
 int do_score_window(const pkv_desc* d, const void* q, const void* k, void* scores, int64_t stride,
                     char* ws, const WsLayout& L, hipStream_t st, bool want_cmax = false, double* rowsum_part = nullptr) {
+  const bool f32 = d->dtype == PKV_F32;
   LogitsParams lp;
-  lp.q = q; lp.k = k;
+  fill_qk(lp, d, q, k);
   lp.logits = ws + L.off_logits;
   lp.partial = reinterpret_cast<float2*>(ws + L.off_partial);
-  lp.B = d->B; lp.H = d->H; lp.S = d->S; lp.w = d->window; lp.G = d->kv_group; lp.D = d->D;
-  lp.fexp = 0; lp.st_mode = 0; lp.logits_bytes = 0;
-  lp.Sp = L.Sp; lp.nT = L.nT; lp.nst = 0; lp.tile = d->D == 256 ? 128 : logits_tile();   // 512-byte rows: 32 keys per wave (register budget)
+  lp.Sp = L.Sp; lp.nT = L.nT; lp.tile = d->D == 256 ? 128 : logits_tile();   // 512-byte rows: 32 keys per wave (register budget)
   if (d->D == 256) lp.nT = (d->S + 127) / 128; lp.nt = logits_nt(); lp.ablate = logits_ablate(); lp.wgtrace = g_wg_trace;
-  lp.qs_b = d->q_stride[0]; lp.qs_h = d->q_stride[1]; lp.qs_s = d->q_stride[2];
-  lp.ks_b = d->k_stride[0]; lp.ks_h = d->k_stride[1]; lp.ks_s = d->k_stride[2];
-  lp.scale_mode = d->scale_mode;
-  lp.sqrt_d = (float)sqrt((double)d->D);   // math.sqrt(head_dim), cast to the fp32 opmath type
-  lp.rcp_sqrt_d = d->dtype == PKV_F32 ? 1.0f / lp.sqrt_d : scale_multiplier(d->dtype, d->D, d->scale_mode);
   const int C = d->kv_group * d->window;
-  int nT_used = L.nT;
+  int nT_used = L.nT, rc;
 #ifdef PKV_DEBUG
   memset(g_score_route, 0, sizeof(g_score_route));
 #endif
-  if (d->dtype == PKV_F32) {
+  if (f32) {
     PKV_SCORE_ROUTE(SR_KERNEL, 3);
     lp.nT = L.nT;
-    {
-      ProfScope ps(PKV_K_LOGITS, st, true);
-      hipError_t e = launch_logits_f32(lp, st);
-      if (e != hipSuccess) return hip_fail(e);
-    }
-    FinalizeParams fp;
-    fp.logits = lp.logits; fp.partial = lp.partial;
-    fp.scores = scores; fp.scores_stride = stride;
-    fp.B = d->B; fp.H = d->H; fp.S = d->S; fp.w = d->window; fp.Sp = L.Sp; fp.nT = L.nT;
-    fp.pool_kind = d->pool_kind;
-    fp.pool_kernel = d->pool_kind == PKV_POOL_NONE ? 1 : d->pool_kernel;
-    fp.reduce = d->reduce;
-    fp.cmax = nullptr; fp.cmax_stride = 0; fp.trace = nullptr; fp.wgtrace = nullptr; fp.rowsum_part = nullptr; fp.rowsum_np = 0;
-    ProfScope ps(PKV_K_FINALIZE, st, true);
-    hipError_t e = launch_finalize_f32(fp, st);
-    return e == hipSuccess ? PKV_OK : hip_fail(e);
-  }
-  if (logits_v2() && C <= 32 && d->D == 128 && !g_wg_trace) {
+    ProfScope ps(PKV_K_LOGITS, st, true);
+    if ((rc = hip_rc(launch_logits_f32(lp, st)))) return rc;
+  } else if (logits_v2() && C <= 32 && d->D == 128 && !g_wg_trace) {
     static int cus = 0;
     if (!cus) {
       int dev = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
     }
-    const int sph = (d->S + 127) / 128;                                     // stages per head group
-    const int64_t total = (int64_t)d->B * (d->H / d->kv_group) * sph;
-    // stages per workgroup.  C <= 8 columns (expanded K/V, window 8): ONE stage per workgroup - measured in round 2 over
-    // {1, 2, 3, 4, 8 stages}: 1 is the fastest at B = 1 (45.1-46.0 us against 45.7-48.6 us for 4 stages in the same
-    // sessions; 2 and 3 stages are the slowest) and at B = 8 (350 vs 353 us): the in-workgroup pipeline only pays when few
-    // workgroups share a CU.  Round 4 tried a chunk-WALKING grid (as many workgroups as the chip holds at once, each walking
-    // chunks blockIdx.x, + gridDim.x, ... with the next chunk's rows in flight): the loop costs 21 registers (one workgroup
-    // per CU less, or spills), C = 8: 44.7 -> 58.7 us at 4 per CU, C = 32: 19.95 -> 19.8 us; and TWO stages of K rows in flight
-    // per workgroup (a second register set: 166 / 204 registers = one workgroup per CU less): C = 8: 44.6 -> 48.4 us, C = 32:
-    // 17.1 -> 21.0 us (19.2 with 4 stages per workgroup).  Both removed (profiles/r04/ab/).
-    // More columns per stage (un-expanded GQA K, C = 32): 4 workgroups per CU with 2..8 stages each
-    // (one stage per workgroup costs +4 us there).  Round 3, after the logits stores moved one stage back (pkv_score.hip):
-    // same ranking - C = 8: 44.3 us at 1 stage, 46.2 / 45.6 / 46.4 / 47.3 at 2 / 4 / 8 / 16; C = 32: 16.8 us at 2 stages
-    // (1024 workgroups), 17.2 at 3, 17.3 at 4, 20.1 at 1 (profiles/r03/ab/defer_stores_ab.txt, one_stage_lds_direct_ab.txt).
-    // Round 4 measured the review's "every finalize workgroup re-merges all partials of its head" (256 per row at one stage per
-    // workgroup): 8 stages per workgroup at B = 8 (32 partials per row) left finalize_kernel at 44.5 us - it is bound by its
-    // ~790 vector instructions per wave, not by those reads - and the K scan at 344 us.  One stage stays.
-    // Round 6: a launch of at most TWO rounds of the chip's 4-per-CU residency (S = 8192 at B = 1: 2048 stages) runs as ONE round of
-    // two-stage workgroups - 14.4 -> 13.5 us there (tools/probes/scan_stages_probe.py); one stage per workgroup stays the
-    // fastest from three rounds up (S = 16384: 25.2 either way, S = 32768: 45.9 against 48-51 us).
-    const int64_t target = logits_v2_wgs() > 0 ? logits_v2_wgs()
-                         : (C > 8 ? (int64_t)4 * cus : (total > (int64_t)4 * cus && total <= (int64_t)8 * cus ? (int64_t)4 * cus : total));
-    int nst = (int)((total + target - 1) / target);
-    nst = std::max(1, std::min(nst, std::min(sph, 64)));
-    lp.nst = nst;
-    lp.nT = nT_used = (sph + nst - 1) / nst;
+    const ScanStages g = logits2_stages(d->B, d->H, d->kv_group, d->S, C, cus, logits_v2_wgs());
+    lp.nst = g.nst;
+    lp.nT = nT_used = g.nT;
     lp.nt = logits_v2_nt();
     lp.fexp = logits_fexp();
     const size_t lbytes = (size_t)d->B * d->H * d->window * L.Sp * 2;
@@ -259,20 +274,18 @@ int do_score_window(const pkv_desc* d, const void* q, const void* k, void* score
     lp.logits_bytes = (uint32_t)std::min<size_t>(lbytes, 0xffffffffull);
 #ifdef PKV_DEBUG
     {                                                                         // what logits2_kernel makes of nst (its `nh`, `edge`)
-      const int L0 = d->S - d->window, span = nst * 128;
+      const int L0 = d->S - d->window, nst = g.nst, span = nst * 128;
       PKV_SCORE_ROUTE(SR_NST, nst); PKV_SCORE_ROUTE(SR_LAST_NH, std::min(nst, (d->S - (lp.nT - 1) * span + 127) / 128));
       PKV_SCORE_ROUTE(SR_STRADDLE_STAGE, L0 / 128 != (d->S - 1) / 128); PKV_SCORE_ROUTE(SR_STRADDLE_WG, L0 / span != (d->S - 1) / span);
       PKV_SCORE_ROUTE(SR_ST_MODE, lp.st_mode); PKV_SCORE_ROUTE(SR_FEXP, lp.fexp);
     }
 #endif
     ProfScope ps(PKV_K_LOGITS, st, true);
-    hipError_t e = launch_logits2(d->dtype, lp, st);
-    if (e != hipSuccess) return hip_fail(e);
+    if ((rc = hip_rc(launch_logits2(d->dtype, lp, st)))) return rc;
   } else {
     nT_used = lp.nT;
     ProfScope ps(PKV_K_LOGITS, st, true);
-    hipError_t e = launch_logits(d->dtype, lp, st);
-    if (e != hipSuccess) return hip_fail(e);
+    if ((rc = hip_rc(launch_logits(d->dtype, lp, st)))) return rc;
   }
   FinalizeParams fp;
   fp.logits = lp.logits; fp.partial = lp.partial;
@@ -281,46 +294,32 @@ int do_score_window(const pkv_desc* d, const void* q, const void* k, void* score
   fp.pool_kind = d->pool_kind;
   fp.pool_kernel = d->pool_kind == PKV_POOL_NONE ? 1 : d->pool_kernel;
   fp.reduce = d->reduce;
-  fp.cmax = want_cmax ? ws + L.off_cmax : nullptr; fp.cmax_stride = L.Lp / 8;
-  fp.trace = g_topk_trace ? g_topk_trace + 8 : nullptr;
-  fp.wgtrace = g_wg_trace;
-  fp.rowsum_part = rowsum_part; fp.rowsum_np = finalize_blocks(d->S, d->window, d->B * d->H);
-  {
-    ProfScope ps(PKV_K_FINALIZE, st, true);
-    hipError_t e = launch_finalize(d->dtype, fp, st);
-    if (e != hipSuccess) return hip_fail(e);
+  if (!f32) {                                            // fp32: no chunk maxima, traces or row sums (nT = L.nT)
+    fp.cmax = want_cmax ? ws + L.off_cmax : nullptr; fp.cmax_stride = L.Lp / 8;
+    fp.trace = g_topk_trace ? g_topk_trace + 8 : nullptr;
+    fp.wgtrace = g_wg_trace;
+    fp.rowsum_part = rowsum_part; fp.rowsum_np = finalize_blocks(d->S, d->window, d->B * d->H);
   }
-  return PKV_OK;
+  ProfScope ps(PKV_K_FINALIZE, st, true);
+  return hip_rc(f32 ? launch_finalize_f32(fp, st) : launch_finalize(d->dtype, fp, st));
 }
 
 int do_score_h2o(const pkv_desc* d, const void* q, const void* k, void* scores, int64_t stride,
                  char* ws, const WsLayout& L, hipStream_t st) {
   H2OParams hp;
-  hp.q = q; hp.k = k;
+  fill_qk(hp, d, q, k);
   hp.rowstat = reinterpret_cast<float*>(ws + L.off_rowstat);
   hp.scores = scores; hp.scores_stride = stride;
-  hp.B = d->B; hp.H = d->H; hp.S = d->S; hp.w = d->window; hp.G = d->kv_group; hp.D = d->D;
-  hp.qs_b = d->q_stride[0]; hp.qs_h = d->q_stride[1]; hp.qs_s = d->q_stride[2];
-  hp.ks_b = d->k_stride[0]; hp.ks_h = d->k_stride[1]; hp.ks_s = d->k_stride[2];
-  hp.scale_mode = d->scale_mode;
-  hp.sqrt_d = (float)sqrt((double)d->D);
-  hp.rcp_sqrt_d = d->dtype == PKV_F32 ? 1.0f / hp.sqrt_d : scale_multiplier(d->dtype, d->D, d->scale_mode);
   if (d->dtype == PKV_F32) {                                                 // both passes of the fp32 form (pkv_f32.hip)
     ProfScope ps(PKV_K_H2O_COLSUM, st);
-    hipError_t e = launch_h2o_f32(hp, st);
-    return e == hipSuccess ? PKV_OK : hip_fail(e);
+    return hip_rc(launch_h2o_f32(hp, st));
   }
   {
     ProfScope ps(PKV_K_H2O_STATS, st, true);                                 // statistics pass
-    hipError_t e = launch_h2o_stats(d->dtype, hp, st);
-    if (e != hipSuccess) return hip_fail(e);
+    if (int rc = hip_rc(launch_h2o_stats(d->dtype, hp, st))) return rc;
   }
-  {
-    ProfScope ps(PKV_K_H2O_COLSUM, st, true);
-    hipError_t e = launch_h2o_colsum(d->dtype, hp, st);
-    if (e != hipSuccess) return hip_fail(e);
-  }
-  return PKV_OK;
+  ProfScope ps(PKV_K_H2O_COLSUM, st, true);
+  return hip_rc(launch_h2o_colsum(d->dtype, hp, st));
 }
 
 constexpr int TK_SEG = 32768;     // segment length of the long-row path (one workgroup's LDS holds up to 57 344 keys)
@@ -349,23 +348,24 @@ size_t topk_tmp_bytes(int rows, int L, int k) {
   return align_up((size_t)rows * cand * 4, 256) + align_up((size_t)rows * cstride * 2, 256) + align_up((size_t)rows * k * 4, 256);
 }
 
-int do_topk(int dtype, int rows, int L, int k, const void* scores, int64_t stride, const int32_t* kpr,
-            int32_t* idx, int64_t idx_stride, hipStream_t st, const void* cmax = nullptr, int64_t cmax_stride = 0,
-            void* tmp = nullptr, size_t tmp_bytes = 0, void* list_out = nullptr, int64_t list_stride = 0,
-            const double* rowsum_part = nullptr, int rowsum_np = 0, int ada_base = 0, int ada_normalize = 0) {
-  if (L < 1 || k < 1 || k > L || rows < 1) return PKV_ERR_SHAPE;
+// what every selection states; a caller adds k_per_row, cmax and the Ada-SnapKV hand-over fields where it has them
+TopkParams topk_params(const void* scores, int64_t stride, int L, int k, int32_t* idx, int64_t idx_stride) {
   TopkParams tp;
-  tp.list_out = list_out; tp.list_stride = list_stride;                               // Ada-SnapKV hand-over (single-workgroup rows only)
-  tp.rowsum_part = rowsum_part; tp.rowsum_np = rowsum_np; tp.ada_base = ada_base; tp.ada_normalize = ada_normalize;
-  if (list_out && (dtype == PKV_F32 || !topk_fits(L, k))) return PKV_ERR_UNSUPPORTED;
-  tp.scores = scores; tp.scores_stride = stride; tp.L = L; tp.k = k; tp.k_per_row = kpr;
-  tp.idx_out = idx; tp.idx_stride = idx_stride; tp.trace = g_topk_trace; tp.wgtrace = g_wg_trace; tp.cmax = cmax; tp.cmax_stride = cmax_stride;
+  tp.scores = scores; tp.scores_stride = stride; tp.L = L; tp.k = k; tp.idx_out = idx; tp.idx_stride = idx_stride;
+  return tp;
+}
+
+// tp: the caller's block (topk_params); Lw, kpad, dual, the segment fields, algo and the trace pointers are set here
+int do_topk(int dtype, int rows, TopkParams tp, void* tmp, size_t tmp_bytes, hipStream_t st) {
+  const int L = tp.L, k = tp.k;
+  if (L < 1 || k < 1 || k > L || rows < 1) return PKV_ERR_SHAPE;
+  if (tp.list_out && (dtype == PKV_F32 || !topk_fits(L, k))) return PKV_ERR_UNSUPPORTED;   // Ada-SnapKV hand-over: single-workgroup rows only
+  tp.trace = g_topk_trace; tp.wgtrace = g_wg_trace;
   tp.nseg = 1; tp.seg_len = 0; tp.algo = topk_algo();
   if (dtype == PKV_F32) {                                  // radix select on 32-bit keys (pkv_f32.hip); k_per_row <= k
     if (k > topk_f32_max_k()) return PKV_ERR_UNSUPPORTED;
     ProfScope ps(PKV_K_TOPK, st, true);
-    hipError_t e = launch_topk_f32(rows, tp, st);
-    return e == hipSuccess ? PKV_OK : hip_fail(e);
+    return hip_rc(launch_topk_f32(rows, tp, st));
   }
   auto launch = [&](int nrows, int Lwg) -> int {     // Lwg = keys one workgroup handles
     const size_t lds = topk_lds_bytes(Lwg, tp.k, &tp.Lw, &tp.kpad);
@@ -373,37 +373,52 @@ int do_topk(int dtype, int rows, int L, int k, const void* scores, int64_t strid
     const size_t xw = (size_t)(tp.kpad > 8192 ? tp.kpad : 8192);
     tp.dual = lds >= (size_t)2 * 16 * tp.Lw + 4 * xw + 4 * 256 + 4 * 64 + 4 * 8192 ? 1 : 0;
     ProfScope ps(PKV_K_TOPK, st, true);
-    hipError_t e = launch_topk(dtype, nrows, tp, lds, st);
-    return e == hipSuccess ? PKV_OK : hip_fail(e);
+    return hip_rc(launch_topk(dtype, nrows, tp, lds, st));
   };
   if (topk_fits(L, k)) return launch(rows, L);
   // long rows: top-k of every 32k segment (row-global indices, canonical order inside the segment), then the top-k of
   // the nseg*k winners.  The candidate list is segment-major, so position order == index order among equal scores and
   // the second selection reproduces (value desc, index asc) of the whole row.
   const size_t need = topk_tmp_bytes(rows, L, k);
-  if (!tmp || tmp_bytes < need || kpr || (reinterpret_cast<uintptr_t>(tmp) & 15) || !topk_long_fits(rows, L, k)) return PKV_ERR_UNSUPPORTED;
+  if (!tmp || tmp_bytes < need || tp.k_per_row || (reinterpret_cast<uintptr_t>(tmp) & 15) || !topk_long_fits(rows, L, k)) return PKV_ERR_UNSUPPORTED;
   const int nseg = (L + TK_SEG - 1) / TK_SEG;
   const int64_t cand = (int64_t)nseg * k, cstride = (int64_t)align_up((size_t)cand, 8);
   char* t8 = static_cast<char*>(tmp);
   int32_t* cand_idx = reinterpret_cast<int32_t*>(t8);
   void* cand_score = t8 + align_up((size_t)rows * cand * 4, 256);
   int32_t* pos = reinterpret_cast<int32_t*>(t8 + align_up((size_t)rows * cand * 4, 256) + align_up((size_t)rows * cstride * 2, 256));
+  int32_t* const idx = tp.idx_out;
+  const int64_t idx_stride = tp.idx_stride;
   tp.nseg = nseg; tp.seg_len = TK_SEG; tp.idx_out = cand_idx; tp.idx_stride = k;
   int rc = launch(rows * nseg, TK_SEG);
   if (rc) return rc;
-  hipError_t e = launch_topk_merge_prep(dtype, rows, L, k, nseg, TK_SEG, scores, stride, cand_idx, cand_score, cstride, st);
-  if (e != hipSuccess) return hip_fail(e);
-  rc = do_topk(dtype, rows, (int)cand, k, cand_score, cstride, nullptr, pos, k, st);
-  if (rc) return rc;
-  e = launch_topk_merge_finish(rows, k, cand_idx, cand, pos, idx, idx_stride, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  if ((rc = hip_rc(launch_topk_merge_prep(dtype, rows, L, k, nseg, TK_SEG, tp.scores, tp.scores_stride, cand_idx, cand_score, cstride, st)))) return rc;
+  if ((rc = do_topk(dtype, rows, topk_params(cand_score, cstride, (int)cand, k, pos, k), nullptr, 0, st))) return rc;
+  return hip_rc(launch_topk_merge_finish(rows, k, cand_idx, cand, pos, idx, idx_stride, st));
+}
+
+SortParams sort_params(const void* scores, int64_t stride, int L, int32_t* sorted_idx, void* sorted_val) {
+  SortParams sp;
+  sp.scores = scores; sp.scores_stride = stride; sp.L = L;
+  sp.n = (L + 7) & ~7;   // raw values + index permutation kept in LDS (2 x 2 B each; keeps the tables 16-B aligned)
+  sp.sorted_idx = sorted_idx; sp.sorted_val = sorted_val; sp.trace = g_topk_trace;
+  return sp;
+}
+
+// what the five budget sites share; each adds its own list / rows / outputs.  L is the row length: a site whose list is shorter sets bp.L
+BudgetParams budget_params(int H, int L, int base, double floor_ratio, int normalize, void* ws) {
+  BudgetParams bp;
+  bp.H = H; bp.L = bp.Lrow = L; bp.base = base;
+  bp.one_minus_floor = (float)(1.0 - floor_ratio);        // python double, then the fp32 scalar of :719
+  bp.floor_capacity = (int)((double)base * floor_ratio);  // int(base_capacity * floor_ratio) (:632)
+  bp.normalize = normalize; bp.ws = ws;
+  return bp;
 }
 
 GatherParams make_gather(const pkv_desc* d, const void* k, const void* v, void* ko, void* vo) {
-  GatherParams g;
-  g.kptr = k; g.vptr = v; g.k_out = ko; g.v_out = vo;
-  g.idx = nullptr; g.idx_stride = 0; g.head_k = nullptr; g.cu_rows = nullptr; g.wgtrace = g_wg_trace;
-  g.rpt = gather_rpt(); g.xcd_map = gather_xcd(); g.nblk = 0;
+  GatherParams g;                       // idx == nullptr: rows 0..k-1; head_k / cu_rows == nullptr: the dense layout
+  g.kptr = k; g.vptr = v; g.k_out = ko; g.v_out = vo; g.wgtrace = g_wg_trace;
+  g.rpt = gather_rpt(); g.xcd_map = gather_xcd();
   g.out_rows = (int64_t)d->B * d->H * (d->topk + d->window);          // dense layout; pkv_gather_flat overrides it
   g.B = d->B; g.H = d->H; g.S = d->S; g.w = d->window; g.nsel = d->topk; g.G = d->kv_group; g.D = d->D;
   g.ks_b = d->k_stride[0]; g.ks_h = d->k_stride[1]; g.ks_s = d->k_stride[2];
@@ -417,14 +432,28 @@ GatherParams make_gather(const pkv_desc* d, const void* k, const void* v, void* 
 
 int do_gather(const GatherParams& g, int max_rows, hipStream_t st) {
   ProfScope ps(PKV_K_GATHER, st, true);
-  hipError_t e = launch_gather(g, max_rows, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_gather(g, max_rows, st));
+}
+
+// score -> top-k -> tie order into idx [B*H][d->topk]: what pkv_compress, pkv_compress_h2o and pkv_select do behind their own
+// argument checks (w = the workspace, L = its layout)
+int do_select(bool h2o, const pkv_desc* d, const void* q, const void* k, int32_t* idx, char* w, const WsLayout& L, hipStream_t st) {
+  void* scores = w + L.off_scores;
+  const bool cm = !h2o && d->dtype != PKV_F32 && topk_cmax() != 0;   // chunk maxima feed the top-k prefilter
+  int rc = h2o ? do_score_h2o(d, q, k, scores, L.Lp, w, L, st) : do_score_window(d, q, k, scores, L.Lp, w, L, st, cm);
+  if (rc) return rc;
+  TopkParams tp = topk_params(scores, L.Lp, d->S - d->window, d->topk, idx, d->topk);
+  tp.cmax = cm ? w + L.off_cmax : nullptr; tp.cmax_stride = L.Lp / 8;
+  if ((rc = do_topk(d->dtype, d->B * d->H, tp, w + L.off_tk, L.tk_bytes, st))) return rc;
+  if (d->tie_order == PKV_TIE_ATEN_ROCM && d->dtype != PKV_F32)               // k <= 32: the order PyTorch-ROCm's topk leaves ties in
+    return hip_rc(launch_aten_small_order(d->dtype, d->B * d->H, d->topk, scores, L.Lp, idx, d->topk, st));
+  return PKV_OK;
 }
 
 int compress_common(bool h2o, const pkv_desc* d, const void* q, const void* k, const void* v, void* k_out,
                     void* v_out, int32_t* idx_out, void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true, true, true);
+  int rc = check_desc(d, NEED_TOPK | SCORING | F32_OK);
   if (rc) return rc;
   if (!q || !k || !v || !k_out || !v_out || !ws) return PKV_ERR_NULL;
   if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out) || misaligned(ws))
@@ -433,19 +462,8 @@ int compress_common(bool h2o, const pkv_desc* d, const void* q, const void* k, c
   if (ws_bytes < (h2o ? L.total : L.off_rowstat)) return PKV_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* w = static_cast<char*>(ws);
-  void* scores = w + L.off_scores;
-  const bool cm = !h2o && d->dtype != PKV_F32 && topk_cmax() != 0;   // chunk maxima feed the top-k prefilter
-  rc = h2o ? do_score_h2o(d, q, k, scores, L.Lp, w, L, st) : do_score_window(d, q, k, scores, L.Lp, w, L, st, cm);
-  if (rc) return rc;
   int32_t* idx = idx_out ? idx_out : reinterpret_cast<int32_t*>(w + L.off_idx);
-  rc = do_topk(d->dtype, d->B * d->H, d->S - d->window, d->topk, scores, L.Lp, nullptr, idx, d->topk, st,
-               cm ? w + L.off_cmax : nullptr, L.Lp / 8,
-               w + L.off_tk, L.tk_bytes);
-  if (rc) return rc;
-  if (d->tie_order == PKV_TIE_ATEN_ROCM && d->dtype != PKV_F32) {             // k <= 32: the order PyTorch-ROCm's topk leaves ties in
-    hipError_t e = launch_aten_small_order(d->dtype, d->B * d->H, d->topk, scores, L.Lp, idx, d->topk, st);
-    if (e != hipSuccess) return hip_fail(e);
-  }
+  if ((rc = do_select(h2o, d, q, k, idx, w, L, st))) return rc;
   GatherParams g = make_gather(d, k, v, k_out, v_out);
   g.idx = idx; g.idx_stride = d->topk;
   return do_gather(g, d->topk + d->window, st);
@@ -486,7 +504,7 @@ size_t pkv_workspace_bytes(const pkv_desc* d) {
 int pkv_score_window(const pkv_desc* d, const void* q, const void* k, void* scores_out,
                      int64_t scores_stride, void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, false, true, true);
+  int rc = check_desc(d, SCORING | F32_OK);
   if (rc) return rc;
   if (!q || !k || !scores_out || !ws) return PKV_ERR_NULL;
   if (misaligned(q) || misaligned(k) || misaligned(scores_out) || misaligned(ws)) return PKV_ERR_ALIGN;
@@ -499,7 +517,7 @@ int pkv_score_window(const pkv_desc* d, const void* q, const void* k, void* scor
 int pkv_score_h2o(const pkv_desc* d, const void* q, const void* k, void* scores_out,
                   int64_t scores_stride, void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, false, true, true);
+  int rc = check_desc(d, SCORING | F32_OK);
   if (rc) return rc;
   if (!q || !k || !scores_out || !ws) return PKV_ERR_NULL;
   if (misaligned(q) || misaligned(k) || misaligned(ws)) return PKV_ERR_ALIGN;
@@ -514,7 +532,9 @@ int pkv_topk(int32_t dtype, int32_t rows, int32_t L, int32_t k, const void* scor
   if (dtype != PKV_BF16 && dtype != PKV_F16 && dtype != PKV_F32) return PKV_ERR_DTYPE;
   if (!scores || !idx_out) return PKV_ERR_NULL;
   if (scores_stride < L || idx_stride < k) return PKV_ERR_SHAPE;
-  return do_topk(dtype, rows, L, k, scores, scores_stride, k_per_row, idx_out, idx_stride, static_cast<hipStream_t>(stream));
+  TopkParams tp = topk_params(scores, scores_stride, L, k, idx_out, idx_stride);
+  tp.k_per_row = k_per_row;
+  return do_topk(dtype, rows, tp, nullptr, 0, static_cast<hipStream_t>(stream));
 }
 
 size_t pkv_topk_workspace_bytes(int32_t rows, int32_t L, int32_t k) { return topk_tmp_bytes(rows, L, k); }
@@ -526,14 +546,15 @@ int pkv_topk_ws(int32_t dtype, int32_t rows, int32_t L, int32_t k, const void* s
   if (!scores || !idx_out) return PKV_ERR_NULL;
   if (scores_stride < L || idx_stride < k) return PKV_ERR_SHAPE;
   if (dtype != PKV_F32 && topk_tmp_bytes(rows, L, k) > 0 && (!ws || ws_bytes < topk_tmp_bytes(rows, L, k))) return PKV_ERR_WORKSPACE;
-  return do_topk(dtype, rows, L, k, scores, scores_stride, k_per_row, idx_out, idx_stride, static_cast<hipStream_t>(stream),
-                 nullptr, 0, ws, ws_bytes);
+  TopkParams tp = topk_params(scores, scores_stride, L, k, idx_out, idx_stride);
+  tp.k_per_row = k_per_row;
+  return do_topk(dtype, rows, tp, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 int pkv_gather_compact(const pkv_desc* d, const void* k, const void* v, const int32_t* idx,
                        int64_t idx_stride, void* k_out, void* v_out, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true, false, true);
+  int rc = check_desc(d, NEED_TOPK | F32_OK);
   if (rc) return rc;
   if (!k || !v || !idx || !k_out || !v_out) return PKV_ERR_NULL;
   if (misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out)) return PKV_ERR_ALIGN;
@@ -546,7 +567,7 @@ int pkv_gather_compact(const pkv_desc* d, const void* k, const void* v, const in
 int pkv_gather_streaming(const pkv_desc* d, const void* k, const void* v, void* k_out, void* v_out,
                          pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true, false, true);
+  int rc = check_desc(d, NEED_TOPK | F32_OK);
   if (rc) return rc;
   if (!k || !v || !k_out || !v_out) return PKV_ERR_NULL;
   if (misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out)) return PKV_ERR_ALIGN;
@@ -568,26 +589,13 @@ int pkv_compress_h2o(const pkv_desc* d, const void* q, const void* k, const void
 int pkv_select(const pkv_desc* d, const void* q, const void* k, int32_t h2o, int32_t* idx_out, void* ws, size_t ws_bytes,
                pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true, true, true);
+  int rc = check_desc(d, NEED_TOPK | SCORING | F32_OK);
   if (rc) return rc;
   if (!q || !k || !idx_out || !ws) return PKV_ERR_NULL;
   if (misaligned(q) || misaligned(k) || misaligned(ws)) return PKV_ERR_ALIGN;
   WsLayout L = ws_layout(d);
   if (ws_bytes < (h2o ? L.total : L.off_rowstat)) return PKV_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  void* scores = w + L.off_scores;
-  const bool cm = !h2o && d->dtype != PKV_F32 && topk_cmax() != 0;
-  rc = h2o ? do_score_h2o(d, q, k, scores, L.Lp, w, L, st) : do_score_window(d, q, k, scores, L.Lp, w, L, st, cm);
-  if (rc) return rc;
-  rc = do_topk(d->dtype, d->B * d->H, d->S - d->window, d->topk, scores, L.Lp, nullptr, idx_out, d->topk, st,
-               cm ? w + L.off_cmax : nullptr, L.Lp / 8, w + L.off_tk, L.tk_bytes);
-  if (rc) return rc;
-  if (d->tie_order == PKV_TIE_ATEN_ROCM && d->dtype != PKV_F32) {
-    hipError_t e = launch_aten_small_order(d->dtype, d->B * d->H, d->topk, scores, L.Lp, idx_out, d->topk, st);
-    if (e != hipSuccess) return hip_fail(e);
-  }
-  return PKV_OK;
+  return do_select(h2o != 0, d, q, k, idx_out, static_cast<char*>(ws), L, static_cast<hipStream_t>(stream));
 }
 
 // ---- L2Norm (pyramidkv_utils.py:405-429): norm scan -> canonical top-k of the negated norms -> gather with w = 0 ----
@@ -597,23 +605,6 @@ struct L2Ws {
   bool sort;                 // cap beyond one top-k workgroup on a row the sort kernel holds: the complete canonical order
   size_t off_scores, off_sel, off_idx, off_tk, tk_bytes, total;
 };
-
-// window == 0 is this entry point's alone (check_desc keeps rejecting it everywhere else)
-int check_l2norm_desc(const pkv_desc* d) {
-  if (d->dtype != PKV_BF16 && d->dtype != PKV_F16 && d->dtype != PKV_F32) return PKV_ERR_DTYPE;
-  if (d->D != 64 && d->D != 128 && d->D != 256) return PKV_ERR_SHAPE;
-  if (d->B < 1 || d->H < 1 || d->S < 1) return PKV_ERR_SHAPE;
-  if (d->kv_group < 1 || d->H % d->kv_group) return PKV_ERR_SHAPE;
-  if (d->window != 0) return PKV_ERR_SHAPE;
-  if (d->topk < 1 || d->topk > d->S) return PKV_ERR_SHAPE;
-  if (d->tie_order != PKV_TIE_CANONICAL && d->tie_order != PKV_TIE_ATEN_ROCM) return PKV_ERR_SHAPE;
-  const int64_t amask = d->dtype == PKV_F32 ? 3 : 7;
-  for (int i = 0; i < 3; ++i)
-    if ((d->k_stride[i] & amask) || (d->v_stride[i] & amask)) return PKV_ERR_ALIGN;
-  if ((int64_t)d->B * d->H > 65535) return PKV_ERR_UNSUPPORTED;
-  if (d->dtype == PKV_F32 && d->topk > topk_f32_max_k()) return PKV_ERR_UNSUPPORTED;
-  return PKV_OK;
-}
 
 L2Ws l2norm_ws(const pkv_desc* d) {
   L2Ws w;
@@ -634,21 +625,21 @@ L2Ws l2norm_ws(const pkv_desc* d) {
 
 size_t pkv_l2norm_workspace_bytes(const pkv_desc* d) {
   PKV_LOAD_DESC(d, 0);
-  if (check_l2norm_desc(d)) return 0;
+  if (check_desc(d, L2NORM | NEED_TOPK | F32_OK)) return 0;
   return l2norm_ws(d).total;
 }
 
 int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k_out, void* v_out, int32_t* idx_out,
                         void* norm_out, void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_l2norm_desc(d);
+  int rc = check_desc(d, L2NORM | NEED_TOPK | F32_OK);
   if (rc) return rc;
   if (!k || !v || !k_out || !v_out || !ws) return PKV_ERR_NULL;
   if (misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out) || misaligned(ws) || misaligned(norm_out))
     return PKV_ERR_ALIGN;
   const L2Ws W = l2norm_ws(d);
   const int S = d->S, cap = d->topk, G = d->kv_group, BH = d->B * d->H;
-  // do_topk's own question, asked before anything is launched (fp32 budgets were bounded by check_l2norm_desc)
+  // do_topk's own question, asked before anything is launched (fp32 budgets were bounded by check_desc)
   if (d->dtype != PKV_F32 && !W.sort && !topk_fits(S, cap) && !topk_long_fits(W.rows_kv, S, cap)) return PKV_ERR_UNSUPPORTED;
   if (ws_bytes < W.total) return PKV_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -659,10 +650,8 @@ int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k
     np.kptr = k; np.neg_out = scores; np.norm_out = norm_out;
     np.B = d->B; np.Hkv = d->H / G; np.S = S; np.D = d->D; np.Lp = W.Lp;
     np.ks_b = d->k_stride[0]; np.ks_h = d->k_stride[1]; np.ks_s = d->k_stride[2];
-    np.nblk = 0; np.norm_vec = 0;
     ProfScope ps(PKV_K_L2NORM, st, true);
-    hipError_t e = launch_l2norm(d->dtype, np, st);
-    if (e != hipSuccess) return hip_fail(e);
+    if ((rc = hip_rc(launch_l2norm(d->dtype, np, st)))) return rc;
   }
   // the selection: one row per KV HEAD (the policy ignores Q: all g query heads of a group keep the same rows)
   int32_t* fin = idx_out ? idx_out : reinterpret_cast<int32_t*>(w + W.off_idx);      // [B*H][cap], what the gather reads
@@ -670,21 +659,13 @@ int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k
   int32_t* sel = direct ? fin : reinterpret_cast<int32_t*>(w + W.off_sel);
   int64_t sel_stride = cap;
   if (W.sort) {
-    SortParams sp;
-    sp.scores = scores; sp.scores_stride = W.Lp; sp.L = S; sp.n = (S + 7) & ~7;
-    sp.sorted_idx = sel; sp.sorted_val = nullptr; sp.trace = g_topk_trace;
     sel_stride = S;
     ProfScope ps(PKV_K_SORT, st);
-    hipError_t e = launch_sort_rows(d->dtype, W.rows_kv, sp, st);
-    if (e != hipSuccess) return hip_fail(e);
-  } else {
-    rc = do_topk(d->dtype, W.rows_kv, S, cap, scores, W.Lp, nullptr, sel, cap, st, nullptr, 0, w + W.off_tk, W.tk_bytes);
-    if (rc) return rc;
+    if ((rc = hip_rc(launch_sort_rows(d->dtype, W.rows_kv, sort_params(scores, W.Lp, S, sel, nullptr), st)))) return rc;
+  } else if ((rc = do_topk(d->dtype, W.rows_kv, topk_params(scores, W.Lp, S, cap, sel, cap), w + W.off_tk, W.tk_bytes, st))) {
+    return rc;
   }
-  if (!direct) {
-    hipError_t e = launch_idx_expand(sel, sel_stride, fin, BH, cap, G, st);
-    if (e != hipSuccess) return hip_fail(e);
-  }
+  if (!direct && (rc = hip_rc(launch_idx_expand(sel, sel_stride, fin, BH, cap, G, st)))) return rc;
   GatherParams g = make_gather(d, k, v, k_out, v_out);      // w = 0: L = S, no window rows behind the selected ones
   g.idx = fin; g.idx_stride = cap;
   return do_gather(g, cap, st);
@@ -718,7 +699,7 @@ size_t pkv_merge_workspace_bytes(const pkv_desc* d) {
 int pkv_merge_compact(const pkv_desc* d, const void* k, const void* v, const int32_t* idx, int64_t idx_stride,
                       void* k_out, void* v_out, void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true, false, true);
+  int rc = check_desc(d, NEED_TOPK | F32_OK);
   if (rc) return rc;
   if (!k || !v || !idx || !k_out || !v_out || !ws) return PKV_ERR_NULL;
   if (misaligned(k) || misaligned(v) || misaligned(k_out) || misaligned(v_out) || misaligned(ws)) return PKV_ERR_ALIGN;
@@ -736,8 +717,7 @@ int pkv_merge_compact(const pkv_desc* d, const void* k, const void* v, const int
   p.drop = reinterpret_cast<int32_t*>(w + m.off_drop); p.pivot = reinterpret_cast<int32_t*>(w + m.off_pivot);
   p.tn = w + m.off_tn; p.ntp = m.ntp; p.D = d->D;
   p.bstart = reinterpret_cast<int32_t*>(w + m.off_start); p.blist = reinterpret_cast<int32_t*>(w + m.off_list);
-  hipError_t e = launch_merge(d->dtype, p, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_merge(d->dtype, p, static_cast<hipStream_t>(stream)));
 }
 
 int pkv_sort_rows(int32_t dtype, int32_t rows, int32_t L, const void* scores, int64_t scores_stride,
@@ -746,15 +726,9 @@ int pkv_sort_rows(int32_t dtype, int32_t rows, int32_t L, const void* scores, in
   if (!scores || !sorted_idx) return PKV_ERR_NULL;
   if (rows < 1 || L < 1 || scores_stride < L) return PKV_ERR_SHAPE;
   if (L > 32768) return PKV_ERR_UNSUPPORTED;
-  SortParams sp;
-  sp.scores = scores; sp.scores_stride = scores_stride; sp.L = L;
-  sp.n = (L + 7) & ~7;   // raw values + index permutation kept in LDS (2 x 2 B each; keeps the tables 16-B aligned)
-  sp.sorted_idx = sorted_idx; sp.sorted_val = sorted_val;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ProfScope ps(PKV_K_SORT, st);
-  sp.trace = g_topk_trace;
-  hipError_t e = launch_sort_rows(dtype, rows, sp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_sort_rows(dtype, rows, sort_params(scores, scores_stride, L, sorted_idx, sorted_val), st));
 }
 
 int pkv_ada_budget(int32_t dtype, int32_t H, int32_t L, const void* sorted_val, int32_t base_capacity,
@@ -763,20 +737,12 @@ int pkv_ada_budget(int32_t dtype, int32_t H, int32_t L, const void* sorted_val, 
   if (dtype != PKV_BF16 && dtype != PKV_F16) return PKV_ERR_DTYPE;
   if (!sorted_val || !head_capacity || !ws) return PKV_ERR_NULL;
   if (H < 1 || H > 256 || L < 1 || base_capacity < 1 || base_capacity > L) return PKV_ERR_SHAPE;
-  if (ws_bytes < 1024 + (size_t)2 * H * 256 * 4) return PKV_ERR_WORKSPACE;
-  BudgetParams bp;
-  bp.trace = nullptr;
-  bp.sorted_idx = nullptr; bp.idx_stride = 0; bp.scores = nullptr; bp.scores_stride = 0; bp.Lrow = L;
-  bp.sorted_val = sorted_val; bp.H = H; bp.L = L; bp.base = base_capacity;
-  bp.one_minus_floor = (float)(1.0 - floor_ratio);                    // python double, then the fp32 scalar of :719
-  bp.floor_capacity = (int)((double)base_capacity * floor_ratio);     // int(base_capacity * floor_ratio) (:632)
-  bp.normalize = normalize; bp.head_capacity = head_capacity; bp.ws = ws; bp.list_ws = nullptr; bp.unsorted = 0;
-  bp.window = 0; bp.head_lens_out = nullptr; bp.cu_klen_out = nullptr; bp.cu_headlens_out = nullptr;
-  bp.host_mirror = nullptr; bp.host_seq = 0; bp.short_list = 0; bp.adaptive_out = nullptr;
+  if (ws_bytes < ada_ws_bytes(H, false)) return PKV_ERR_WORKSPACE;
+  BudgetParams bp = budget_params(H, L, base_capacity, floor_ratio, normalize, ws);
+  bp.sorted_val = sorted_val; bp.head_capacity = head_capacity;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ProfScope ps(PKV_K_BUDGET, st);
-  hipError_t e = launch_budget(dtype, bp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_budget(dtype, bp, st));
 }
 
 int pkv_ada_budget_topm(int32_t dtype, int32_t H, int32_t L, int32_t M, const void* scores, int64_t scores_stride,
@@ -791,20 +757,13 @@ int pkv_ada_budget_topm(int32_t dtype, int32_t H, int32_t L, int32_t M, const vo
   const int64_t need = std::min<int64_t>(L, (int64_t)H * base_capacity);
   if (M < need || M > L || scores_stride < L || idx_stride < M) return PKV_ERR_SHAPE;
   if (M > 65536) return PKV_ERR_UNSUPPORTED;          // the staged list must fit in LDS (2 bytes per entry)
-  if (ws_bytes < 1024 + (size_t)2 * H * 256 * 4) return PKV_ERR_WORKSPACE;
-  BudgetParams bp;
-  bp.trace = nullptr;
-  bp.sorted_val = nullptr; bp.sorted_idx = top_idx; bp.idx_stride = idx_stride; bp.scores = scores; bp.scores_stride = scores_stride;
-  bp.Lrow = L; bp.H = H; bp.L = M; bp.base = base_capacity;
-  bp.one_minus_floor = (float)(1.0 - floor_ratio);
-  bp.floor_capacity = (int)((double)base_capacity * floor_ratio);
-  bp.normalize = normalize; bp.head_capacity = head_capacity; bp.ws = ws; bp.list_ws = nullptr; bp.unsorted = 0;
-  bp.window = window; bp.head_lens_out = head_lens; bp.cu_klen_out = cu_klen; bp.cu_headlens_out = nullptr;
-  bp.host_mirror = nullptr; bp.host_seq = 0; bp.short_list = 0; bp.adaptive_out = nullptr;
+  if (ws_bytes < ada_ws_bytes(H, false)) return PKV_ERR_WORKSPACE;
+  BudgetParams bp = budget_params(H, L, base_capacity, floor_ratio, normalize, ws);
+  bp.sorted_idx = top_idx; bp.idx_stride = idx_stride; bp.scores = scores; bp.scores_stride = scores_stride; bp.L = M;
+  bp.head_capacity = head_capacity; bp.window = window; bp.head_lens_out = head_lens; bp.cu_klen_out = cu_klen;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ProfScope ps(PKV_K_BUDGET, st);
-  hipError_t e = launch_budget(dtype, bp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_budget(dtype, bp, st));
 }
 
 int pkv_ada_budget_rows(int32_t dtype, int32_t H, int32_t L, const void* scores, int64_t scores_stride, int32_t base_capacity,
@@ -818,20 +777,14 @@ int pkv_ada_budget_rows(int32_t dtype, int32_t H, int32_t L, const void* scores,
   if (reinterpret_cast<uintptr_t>(host_mirror) & 7) return PKV_ERR_ALIGN;          // 64-bit words since 0.2.0 (was int32 [H+1] before)
   if (host_mirror && host_seq < 0) return PKV_ERR_SHAPE;
   if (L > (dtype == PKV_F32 ? budget_f32_max_row() : 65536)) return PKV_ERR_UNSUPPORTED;   // a row lives in the registers of one 1024-thread workgroup
-  if (ws_bytes < (dtype == PKV_F32 ? 1024 + (size_t)4 * H * 256 * 4 + (size_t)4 * H * 4 : 1024 + (size_t)2 * H * 256 * 4)) return PKV_ERR_WORKSPACE;
-  BudgetParams bp;
-  bp.trace = nullptr;
-  bp.sorted_val = nullptr; bp.sorted_idx = nullptr; bp.idx_stride = 0; bp.scores = scores; bp.scores_stride = scores_stride;
-  bp.Lrow = L; bp.H = H; bp.L = L; bp.base = base_capacity;
-  bp.one_minus_floor = (float)(1.0 - floor_ratio);
-  bp.floor_capacity = (int)((double)base_capacity * floor_ratio);
-  bp.normalize = normalize; bp.head_capacity = head_capacity; bp.ws = ws; bp.list_ws = nullptr; bp.unsorted = 1;
-  bp.window = window; bp.head_lens_out = head_lens; bp.cu_klen_out = cu_klen; bp.cu_headlens_out = cu_headlens;
-  bp.host_mirror = reinterpret_cast<unsigned long long*>(host_mirror); bp.host_seq = host_seq; bp.short_list = 0; bp.adaptive_out = nullptr;
+  if (ws_bytes < ada_ws_bytes(H, dtype == PKV_F32)) return PKV_ERR_WORKSPACE;
+  BudgetParams bp = budget_params(H, L, base_capacity, floor_ratio, normalize, ws);
+  bp.scores = scores; bp.scores_stride = scores_stride; bp.unsorted = 1;
+  bp.head_capacity = head_capacity; bp.window = window; bp.head_lens_out = head_lens; bp.cu_klen_out = cu_klen; bp.cu_headlens_out = cu_headlens;
+  bp.host_mirror = reinterpret_cast<unsigned long long*>(host_mirror); bp.host_seq = host_seq;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ProfScope ps(PKV_K_BUDGET, st);
-  hipError_t e = dtype == PKV_F32 ? launch_budget_f32(bp, st) : launch_budget(dtype, bp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(dtype == PKV_F32 ? launch_budget_f32(bp, st) : launch_budget(dtype, bp, st));
 }
 
 int pkv_ada_adaptive_lists(int32_t dtype, int32_t H, int32_t L, int32_t M, const void* scores, int64_t scores_stride,
@@ -842,19 +795,14 @@ int pkv_ada_adaptive_lists(int32_t dtype, int32_t H, int32_t L, int32_t M, const
   if (H < 1 || L < 1 || M < 1 || M > L || base_capacity < 1 || base_capacity > M) return PKV_ERR_SHAPE;
   if (scores_stride < L || idx_stride < M) return PKV_ERR_SHAPE;
   if (M > 65536) return PKV_ERR_UNSUPPORTED;
-  if (ws_bytes < 1024 + (size_t)2 * H * 256 * 4) return PKV_ERR_WORKSPACE;
-  BudgetParams bp;
-  bp.trace = nullptr;
-  bp.sorted_val = nullptr; bp.sorted_idx = top_idx; bp.idx_stride = idx_stride; bp.scores = scores; bp.scores_stride = scores_stride;
-  bp.Lrow = L; bp.H = H; bp.L = M; bp.base = base_capacity;
-  bp.one_minus_floor = 1.0f; bp.floor_capacity = 0;
-  bp.normalize = normalize; bp.head_capacity = nullptr; bp.ws = ws; bp.list_ws = nullptr; bp.unsorted = 0;
-  bp.window = 0; bp.head_lens_out = nullptr; bp.cu_klen_out = nullptr; bp.cu_headlens_out = nullptr;
-  bp.host_mirror = nullptr; bp.host_seq = 0; bp.short_list = 0; bp.adaptive_out = lists_out;
+  if (ws_bytes < ada_ws_bytes(H, false)) return PKV_ERR_WORKSPACE;
+  BudgetParams bp = budget_params(H, L, base_capacity, 0.0, normalize, ws);
+  bp.one_minus_floor = 1.0f; bp.floor_capacity = 0;                   // no floor: the lists are all that is asked for
+  bp.sorted_idx = top_idx; bp.idx_stride = idx_stride; bp.scores = scores; bp.scores_stride = scores_stride; bp.L = M;
+  bp.adaptive_out = lists_out;
   hipStream_t st = static_cast<hipStream_t>(stream);
   ProfScope ps(PKV_K_BUDGET, st);
-  hipError_t e = launch_budget(dtype, bp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_budget(dtype, bp, st));
 }
 
 int pkv_ada_select(const pkv_desc* d, const void* q, const void* k, int32_t base_capacity, double floor_ratio,
@@ -862,7 +810,7 @@ int pkv_ada_select(const pkv_desc* d, const void* q, const void* k, int32_t base
                    int32_t* head_lens, int32_t* cu_klen, int32_t* cu_headlens, uint64_t* host_mirror, int32_t host_seq,
                    void* ws, size_t ws_bytes, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, true);
+  int rc = check_desc(d, NEED_TOPK | SCORING);
   if (rc) return rc;
   if (d->B != 1) return PKV_ERR_SHAPE;                     // reference asserts bsz == 1 (:724)
   if (!q || !k || !top_idx || !head_lens || !cu_klen || !ws) return PKV_ERR_NULL;
@@ -892,42 +840,36 @@ int pkv_ada_select(const pkv_desc* d, const void* q, const void* k, int32_t base
   double* rowsum = reinterpret_cast<double*>(w + W.off_ada + 1024);           // [H][np] doubles inside the (then unused) count tables
   rc = do_score_window(d, q, k, scores, W.Lp, w, W, st, cm, fused ? rowsum : nullptr);
   if (rc) return rc;
-  rc = do_topk(d->dtype, H, L, M, scores, W.Lp, nullptr, top_idx, M, st, cm ? w + W.off_cmax : nullptr, W.Lp / 8,
-               w + W.off_tk, W.tk_bytes, fused ? w + W.off_ada_list : nullptr, Lpad, rowsum, np, base_capacity, normalize ? 1 : 0);
-  if (rc) return rc;
-  if (given_capacity) {                                    // HeadKV: capacities come from the host (:855); metadata only
-    hipError_t e = launch_ada_metadata(H, d->window, given_capacity, head_lens, cu_klen, st, cu_headlens);
-    return e == hipSuccess ? PKV_OK : hip_fail(e);
-  }
-  BudgetParams bp;
-  bp.trace = nullptr;
-  bp.sorted_val = nullptr; bp.sorted_idx = top_idx; bp.idx_stride = M; bp.scores = scores; bp.scores_stride = W.Lp;
-  bp.Lrow = L; bp.H = H; bp.L = M; bp.base = base_capacity;
-  bp.one_minus_floor = (float)(1.0 - floor_ratio);
-  bp.floor_capacity = (int)((double)base_capacity * floor_ratio);
-  bp.normalize = normalize; bp.head_capacity = head_capacity; bp.ws = w + W.off_ada; bp.list_ws = w + W.off_ada_list; bp.unsorted = 0;
+  TopkParams tp = topk_params(scores, W.Lp, L, M, top_idx, M);
+  tp.cmax = cm ? w + W.off_cmax : nullptr; tp.cmax_stride = W.Lp / 8;
+  tp.list_out = fused ? w + W.off_ada_list : nullptr; tp.list_stride = Lpad;
+  tp.rowsum_part = rowsum; tp.rowsum_np = np; tp.ada_base = base_capacity; tp.ada_normalize = normalize ? 1 : 0;
+  if ((rc = do_topk(d->dtype, H, tp, w + W.off_tk, W.tk_bytes, st))) return rc;
+  if (given_capacity)                                      // HeadKV: capacities come from the host (:855); metadata only
+    return hip_rc(launch_ada_metadata(H, d->window, given_capacity, head_lens, cu_klen, st, cu_headlens));
+  BudgetParams bp = budget_params(H, L, base_capacity, floor_ratio, normalize, w + W.off_ada);
+  bp.sorted_idx = top_idx; bp.idx_stride = M; bp.scores = scores; bp.scores_stride = W.Lp; bp.L = M;
+  bp.head_capacity = head_capacity; bp.list_ws = w + W.off_ada_list;
   bp.window = d->window; bp.head_lens_out = head_lens; bp.cu_klen_out = cu_klen; bp.cu_headlens_out = cu_headlens;
-  bp.host_mirror = reinterpret_cast<unsigned long long*>(host_mirror); bp.host_seq = host_seq; bp.adaptive_out = nullptr;
+  bp.host_mirror = reinterpret_cast<unsigned long long*>(host_mirror); bp.host_seq = host_seq;
   bp.short_list = M < std::min<int64_t>(L, (int64_t)H * base_capacity) ? 1 : 0;
   bp.trace = g_topk_trace ? g_topk_trace + 16 : nullptr;      // debug build: the caller's buffer holds 32 stamps
   ProfScope ps(PKV_K_BUDGET, st, fused);            // one launch: its own begin / end (three launches: a bracket of event records)
-  hipError_t e = fused ? launch_ada_fused(bp, w + W.off_ada_list, Lpad, st) : launch_budget(d->dtype, bp, st);
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(fused ? launch_ada_fused(bp, w + W.off_ada_list, Lpad, st) : launch_budget(d->dtype, bp, st));
 }
 
 int pkv_ada_metadata(int32_t H, int32_t window, const int32_t* head_capacity, int32_t* head_lens,
                      int32_t* cu_klen, pkv_stream_t stream) {
   if (!head_capacity || !head_lens || !cu_klen) return PKV_ERR_NULL;
   if (H < 1) return PKV_ERR_SHAPE;
-  hipError_t e = launch_ada_metadata(H, window, head_capacity, head_lens, cu_klen, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_ada_metadata(H, window, head_capacity, head_lens, cu_klen, static_cast<hipStream_t>(stream)));
 }
 
 int pkv_gather_flat(const pkv_desc* d, const void* k, const void* v, const int32_t* sorted_idx,
                     int64_t idx_stride, const int32_t* head_capacity, const int32_t* cu_klen,
                     void* k_out, void* v_out, int64_t out_rows, pkv_stream_t stream) {
   PKV_LOAD_DESC(d, rc_ld);
-  int rc = check_desc(d, false, false, true);      // fp32 rows move as 2D 16-bit elements (make_gather)
+  int rc = check_desc(d, F32_OK);     // fp32 rows move as 2D 16-bit elements (make_gather)
   if (rc) return rc;
   if (d->B != 1) return PKV_ERR_SHAPE;   // reference asserts bsz == 1 (:724)
   if (!k || !v || !sorted_idx || !head_capacity || !cu_klen || !k_out || !v_out) return PKV_ERR_NULL;
@@ -949,8 +891,7 @@ int pkv_update_flatten_view(int32_t dtype, int32_t H, int32_t head_dim, const vo
   FlattenParams fp;
   fp.cache = cache; fp.state = state; fp.head_lens = head_lens; fp.cu_klen = cu_klen; fp.out = out;
   fp.H = H; fp.row_bytes = head_dim * (dtype == PKV_F32 ? 4 : 2);
-  hipError_t e = launch_flatten(fp, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_flatten(fp, static_cast<hipStream_t>(stream)));
 }
 
 /* ---- debug / test hooks (not part of the drop-in surface) ---- */
@@ -969,7 +910,7 @@ int pkv_debug_merge_route(int32_t* out, int n) {
   if (g_merge_flags) {
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(&flags, g_merge_flags, 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e);
+    if (e != hipSuccess) return hip_rc(e);
   }
   g_merge_route[MR_FLAGS] = (int)flags;
   for (int i = 0; i < n && i < MR_WORDS; ++i) out[i] = g_merge_route[i];
@@ -991,21 +932,18 @@ int pkv_runtime_reset(void) {
 float pkv_debug_scale_multiplier(int32_t dtype, int32_t D, int32_t scale_mode) { return scale_multiplier(dtype, D, scale_mode); }
 
 int pkv_debug_exp(const float* in, float* out, int64_t n, pkv_stream_t stream) {
-  hipError_t e = launch_debug_exp(in, out, n, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_debug_exp(in, out, n, static_cast<hipStream_t>(stream)));
 }
 
 int pkv_debug_sqrt(const float* in, float* out, int64_t n, pkv_stream_t stream) {
   if (!in || !out) return PKV_ERR_NULL;
   if (n < 1) return PKV_ERR_SHAPE;
-  hipError_t e = launch_debug_sqrt(in, out, n, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_debug_sqrt(in, out, n, static_cast<hipStream_t>(stream)));
 }
 
 int pkv_debug_round(int32_t dtype, const float* in, void* out, int64_t n, pkv_stream_t stream) {
   if (dtype != PKV_BF16 && dtype != PKV_F16) return PKV_ERR_DTYPE;
-  hipError_t e = launch_debug_round(dtype, in, static_cast<uint16_t*>(out), n, static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+  return hip_rc(launch_debug_round(dtype, in, static_cast<uint16_t*>(out), n, static_cast<hipStream_t>(stream)));
 }
 
 int pkv_debug_unit_div(int32_t dtype, const void* x, const void* norm, void* out_div, void* out_divc, void* out_mul, void* out_mul_ok,
@@ -1013,10 +951,9 @@ int pkv_debug_unit_div(int32_t dtype, const void* x, const void* norm, void* out
   if (dtype != PKV_BF16 && dtype != PKV_F16) return PKV_ERR_DTYPE;
   if (!x || !norm || !out_div || !out_divc || !out_mul || !out_mul_ok) return PKV_ERR_NULL;
   if (n < 1) return PKV_ERR_SHAPE;
-  hipError_t e = launch_debug_unit_div(dtype, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(norm), static_cast<uint16_t*>(out_div),
+  return hip_rc(launch_debug_unit_div(dtype, static_cast<const uint16_t*>(x), static_cast<const uint16_t*>(norm), static_cast<uint16_t*>(out_div),
                                        static_cast<uint16_t*>(out_divc), static_cast<uint16_t*>(out_mul), static_cast<uint8_t*>(out_mul_ok), n,
-                                       static_cast<hipStream_t>(stream));
-  return e == hipSuccess ? PKV_OK : hip_fail(e);
+                                       static_cast<hipStream_t>(stream)));
 }
 
 int pkv_prof_enable(int on) {
@@ -1029,11 +966,9 @@ int pkv_prof_enable(int on) {
 int pkv_prof_read(double* ms_sum, int64_t* launches, int reset) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
   for (auto& r : g_pending) {
-    hipError_t e = hipEventSynchronize(r.b);
-    if (e != hipSuccess) return hip_fail(e);
     float ms = 0.f;
-    e = hipEventElapsedTime(&ms, r.a, r.b);
-    if (e != hipSuccess) return hip_fail(e);
+    if (int rc = hip_rc(hipEventSynchronize(r.b))) return rc;
+    if (int rc = hip_rc(hipEventElapsedTime(&ms, r.a, r.b))) return rc;
     g_ms[r.id] += ms;
     g_n[r.id] += 1;
     g_free_events.push_back(r.a);

@@ -111,184 +111,184 @@ extern const unsigned int* g_merge_flags;      // device address of the flags wo
 #endif
 
 struct LogitsParams {
-  unsigned long long* wgtrace;   // debug: per-workgroup (start,end) wall clock, may be null
-  const void* q;
-  const void* k;
-  void* logits;      // [B*H*w][Sp] model dtype
-  float2* partial;   // [B*H*w][nT] (tile row max, tile sum exp)
-  int B, H, S, w, G; // G = kv_group
-  int D;             // head size: 64, 128 or 256 (logits2_kernel: 128 only)
-  int Sp, nT;
-  int tile;          // keys per workgroup: 128 or 256 (nT = ceil(S / tile))
-  int nt;            // nontemporal K loads
-  int nst;           // logits2_kernel: 128-key stages per workgroup (nT = chunks per head)
-  int ablate;        // 0 = full kernel; 1..3 = measurement-only ablations (PKV_LOGITS_ABLATE)
-  int fexp;          // logits2_kernel: hardware exp2 for the partial (max, sum exp) statistics
-  int st_mode;       // logits2_kernel: logits stores 0 = plain, 1 = nontemporal, 2 = write-through (sc1)
-  uint32_t logits_bytes;   // extent of the logits buffer (raw-buffer stores)
-  int64_t qs_b, qs_h, qs_s;
-  int64_t ks_b, ks_h, ks_s;
-  int scale_mode;
-  float sqrt_d, rcp_sqrt_d;
+  unsigned long long* wgtrace = nullptr; // debug: per-workgroup (start,end) wall clock, may be null
+  const void* q = nullptr;
+  const void* k = nullptr;
+  void* logits = nullptr; // [B*H*w][Sp] model dtype
+  float2* partial = nullptr; // [B*H*w][nT] (tile row max, tile sum exp)
+  int B = 0, H = 0, S = 0, w = 0, G = 0; // G = kv_group
+  int D = 0;         // head size: 64, 128 or 256 (logits2_kernel: 128 only)
+  int Sp = 0, nT = 0;
+  int tile = 0;      // keys per workgroup: 128 or 256 (nT = ceil(S / tile))
+  int nt = 0;        // nontemporal K loads
+  int nst = 0;       // logits2_kernel: 128-key stages per workgroup (nT = chunks per head)
+  int ablate = 0;    // 0 = full kernel; 1..3 = measurement-only ablations (PKV_LOGITS_ABLATE)
+  int fexp = 0;      // logits2_kernel: hardware exp2 for the partial (max, sum exp) statistics
+  int st_mode = 0;   // logits2_kernel: logits stores 0 = plain, 1 = nontemporal, 2 = write-through (sc1)
+  uint32_t logits_bytes = 0; // extent of the logits buffer (raw-buffer stores)
+  int64_t qs_b = 0, qs_h = 0, qs_s = 0;
+  int64_t ks_b = 0, ks_h = 0, ks_s = 0;
+  int scale_mode = 0;
+  float sqrt_d = 0, rcp_sqrt_d = 0;
 };
 
 struct FinalizeParams {
-  const void* logits;
-  const float2* partial;
-  void* scores;          // [B*H][scores_stride]
-  int64_t scores_stride;
-  int B, H, S, w, Sp, nT;
-  int pool_kind, pool_kernel, reduce;
-  void* cmax;            // [B*H][cmax_stride] max pooled score of every 8-position chunk (may be null)
-  int64_t cmax_stride;
-  unsigned long long* trace;   // debug: phase timestamps of block (0,0) (may be null)
-  unsigned long long* wgtrace;
+  const void* logits = nullptr;
+  const float2* partial = nullptr;
+  void* scores = nullptr; // [B*H][scores_stride]
+  int64_t scores_stride = 0;
+  int B = 0, H = 0, S = 0, w = 0, Sp = 0, nT = 0;
+  int pool_kind = 0, pool_kernel = 0, reduce = 0;
+  void* cmax = nullptr;   // [B*H][cmax_stride] max pooled score of every 8-position chunk (may be null)
+  int64_t cmax_stride = 0;
+  unsigned long long* trace = nullptr; // debug: phase timestamps of block (0,0) (may be null)
+  unsigned long long* wgtrace = nullptr;
   // Ada-SnapKV (round 5): the sum over ALL pooled scores of a row (:710 `attn_score.sum(dim=-1)`) as one fp64 partial per
   // workgroup, [B*H][rowsum_np] with rowsum_np = the grid's x dimension (1024 positions each); added in workgroup order by the
   // budget kernel (a fixed order: run-to-run identical).  May be null.
-  double* rowsum_part;
-  int rowsum_np;
+  double* rowsum_part = nullptr;
+  int rowsum_np = 0;
 };
 
 struct TopkParams {
-  const void* scores;    // [rows][scores_stride] model dtype
-  int64_t scores_stride;
-  int L, k;
-  const int32_t* k_per_row;
-  const void* cmax;      // optional: per-chunk (8 scores) maxima written by finalize_kernel, [rows][cmax_stride]
-  int64_t cmax_stride;
-  int32_t* idx_out;      // [rows][idx_stride]
-  int64_t idx_stride;
-  unsigned long long* trace;   // debug: phase timestamps of row 0 (may be null)
-  unsigned long long* wgtrace;
-  int Lw;                // keys per wave (multiple of 512)
-  int kpad;              // words reserved for the selection list (see topk_lds_bytes)
-  int dual;              // second 32 KB counter / radix scratch region present in LDS
-  int algo;              // small-k fast path: 1 = one-level histogram + bucket counting sort, 0 = two-level select + radix ordering
-  int nseg, seg_len;     // long rows: workgroup r handles segment r % nseg (seg_len keys) of row r / nseg and writes
+  const void* scores = nullptr; // [rows][scores_stride] model dtype
+  int64_t scores_stride = 0;
+  int L = 0, k = 0;
+  const int32_t* k_per_row = nullptr;
+  const void* cmax = nullptr; // optional: per-chunk (8 scores) maxima written by finalize_kernel, [rows][cmax_stride]
+  int64_t cmax_stride = 0;
+  int32_t* idx_out = nullptr; // [rows][idx_stride]
+  int64_t idx_stride = 0;
+  unsigned long long* trace = nullptr; // debug: phase timestamps of row 0 (may be null)
+  unsigned long long* wgtrace = nullptr;
+  int Lw = 0;            // keys per wave (multiple of 512)
+  int kpad = 0;          // words reserved for the selection list (see topk_lds_bytes)
+  int dual = 0;          // second 32 KB counter / radix scratch region present in LDS
+  int algo = 0;          // small-k fast path: 1 = one-level histogram + bucket counting sort, 0 = two-level select + radix ordering
+  int nseg = 0, seg_len = 0; // long rows: workgroup r handles segment r % nseg (seg_len keys) of row r / nseg and writes
                          // row-global indices to idx_out row r; L stays the full row length.  nseg <= 1: off
   // Ada-SnapKV (round 5, topk_kernel<T, true>): the selection also hands over every head's ADAPTIVE list (:706-711) as
   // order-preserving 16-bit keys in output order: the winners' raw scores, times the head's ratio sum(top base) / sum(all)
   // (:710; the row total comes from finalize_kernel's per-workgroup fp64 partials), rounded to the model dtype (:711).  The
   // budget step then only has to find the global threshold over those keys.
-  void* list_out;            // [rows][list_stride] uint16 keys, or null
-  int64_t list_stride;
-  const double* rowsum_part; // [rows][rowsum_np] finalize_kernel's partial sums of the row (normalize only)
-  int rowsum_np;
-  int ada_base;              // base capacity: the ratio's numerator sums the first ada_base entries of the list
-  int ada_normalize;
+  void* list_out = nullptr;   // [rows][list_stride] uint16 keys, or null
+  int64_t list_stride = 0;
+  const double* rowsum_part = nullptr; // [rows][rowsum_np] finalize_kernel's partial sums of the row (normalize only)
+  int rowsum_np = 0;
+  int ada_base = 0;          // base capacity: the ratio's numerator sums the first ada_base entries of the list
+  int ada_normalize = 0;
 };
 
 struct SortParams {
-  const void* scores;
-  int64_t scores_stride;
-  int L, n;              // n = power of two >= L
-  int32_t* sorted_idx;   // [rows][L]
-  void* sorted_val;      // [rows][L] or null
-  unsigned long long* trace;   // debug: phase stamps of row 0 (may be null)
+  const void* scores = nullptr;
+  int64_t scores_stride = 0;
+  int L = 0, n = 0;      // n = power of two >= L
+  int32_t* sorted_idx = nullptr; // [rows][L]
+  void* sorted_val = nullptr; // [rows][L] or null
+  unsigned long long* trace = nullptr; // debug: phase stamps of row 0 (may be null)
 };
 
 struct GatherParams {
-  unsigned long long* wgtrace;   // debug: per-workgroup (start,end) wall clock, may be null
-  const void* kptr;
-  const void* vptr;
-  void* k_out;
-  void* v_out;
-  const int32_t* idx;        // [B*H][idx_stride] or null (identity: StreamingLLM)
-  int64_t idx_stride;
-  const int32_t* head_k;     // per-(b,h) selected count (flat layout) or null -> uniform k
-  const int32_t* cu_rows;    // per-(b,h) first output row (flat layout) or null -> bh*(k+w)
-  int B, H, S, w, nsel, G;   // nsel = uniform selected-row count k
-  int D;                     // head size: 64, 128 or 256 (a row is D*2 bytes = D/8 lanes x 16 B)
-  int64_t ks_b, ks_h, ks_s;
-  int64_t vs_b, vs_h, vs_s;
-  int rpt;                   // rows per lane and tensor: 2, 4 or 8 (16*rpt rows per workgroup)
-  int xcd_map;               // place the blocks of head bh on XCD bh % 8 (where top-k wrote its indices)
-  int nblk;                  // row blocks per head (set by launch_gather)
-  int64_t out_rows;          // rows the output buffers hold: nothing is stored at or beyond it
+  unsigned long long* wgtrace = nullptr; // debug: per-workgroup (start,end) wall clock, may be null
+  const void* kptr = nullptr;
+  const void* vptr = nullptr;
+  void* k_out = nullptr;
+  void* v_out = nullptr;
+  const int32_t* idx = nullptr; // [B*H][idx_stride] or null (identity: StreamingLLM)
+  int64_t idx_stride = 0;
+  const int32_t* head_k = nullptr; // per-(b,h) selected count (flat layout) or null -> uniform k
+  const int32_t* cu_rows = nullptr; // per-(b,h) first output row (flat layout) or null -> bh*(k+w)
+  int B = 0, H = 0, S = 0, w = 0, nsel = 0, G = 0; // nsel = uniform selected-row count k
+  int D = 0;                 // head size: 64, 128 or 256 (a row is D*2 bytes = D/8 lanes x 16 B)
+  int64_t ks_b = 0, ks_h = 0, ks_s = 0;
+  int64_t vs_b = 0, vs_h = 0, vs_s = 0;
+  int rpt = 0;               // rows per lane and tensor: 2, 4 or 8 (16*rpt rows per workgroup)
+  int xcd_map = 0;           // place the blocks of head bh on XCD bh % 8 (where top-k wrote its indices)
+  int nblk = 0;              // row blocks per head (set by launch_gather)
+  int64_t out_rows = 0;      // rows the output buffers hold: nothing is stored at or beyond it
 };
 
 struct BudgetParams {
-  const void* sorted_val;    // [H][L] descending, or null when the list is given as (sorted_idx, scores)
-  const int32_t* sorted_idx; // [H][idx_stride]: the first L entries of every head's descending order (top-L indices), or null
-  int64_t idx_stride;
-  const void* scores;        // [H][scores_stride] un-sorted score rows of length Lrow (with sorted_idx)
-  int64_t scores_stride;
-  int Lrow;
-  int H, L, base;            // L = entries per head in the sorted list
-  float one_minus_floor;     // (float)(1.0 - floor_ratio), the fp32 scalar ATen multiplies by
-  int floor_capacity;        // int(base * floor_ratio)
-  int normalize;
-  int32_t* head_capacity;    // [H]
-  int window;                // with head_lens_out / cu_klen_out: the var-len metadata of :682-691 from the same launch
-  int32_t* head_lens_out;    // [H] or null
-  int32_t* cu_klen_out;      // [H+1] or null
-  int32_t* cu_headlens_out;  // [H] inclusive prefix (:687) or null
-  void* adaptive_out;        // optional: dtype [H][L] - emit every head's adaptive list (:711) and stop (head-sharded exchange)
-  unsigned long long* host_mirror;   // optional: device-visible PINNED HOST memory, uint64 [H]: word h = host_seq << 32 | ran_out << 31 | cap_h
-  int32_t host_seq;
-  int short_list;            // the lists are SHORTER than min(L, H*base): bit 31 of the mirror words reports a head whose list ran out
-  int unsorted;              // 1: `scores` are the un-sorted rows [H][scores_stride] of length Lrow and no list is given
-  void* list_ws;             // optional: H * roundup(L,8) * 2 bytes, 16-B aligned - the looked-up lists travel through it
-  void* ws;                  // 1024 B ratios + 2 * H*256 int32
-  unsigned long long* trace; // debug: phase timestamps of the one-launch budget kernel (may be null)
+  const void* sorted_val = nullptr; // [H][L] descending, or null when the list is given as (sorted_idx, scores)
+  const int32_t* sorted_idx = nullptr; // [H][idx_stride]: the first L entries of every head's descending order (top-L indices), or null
+  int64_t idx_stride = 0;
+  const void* scores = nullptr; // [H][scores_stride] un-sorted score rows of length Lrow (with sorted_idx)
+  int64_t scores_stride = 0;
+  int Lrow = 0;
+  int H = 0, L = 0, base = 0; // L = entries per head in the sorted list
+  float one_minus_floor = 0; // (float)(1.0 - floor_ratio), the fp32 scalar ATen multiplies by
+  int floor_capacity = 0;    // int(base * floor_ratio)
+  int normalize = 0;
+  int32_t* head_capacity = nullptr; // [H]
+  int window = 0;            // with head_lens_out / cu_klen_out: the var-len metadata of :682-691 from the same launch
+  int32_t* head_lens_out = nullptr; // [H] or null
+  int32_t* cu_klen_out = nullptr; // [H+1] or null
+  int32_t* cu_headlens_out = nullptr; // [H] inclusive prefix (:687) or null
+  void* adaptive_out = nullptr; // optional: dtype [H][L] - emit every head's adaptive list (:711) and stop (head-sharded exchange)
+  unsigned long long* host_mirror = nullptr; // optional: device-visible PINNED HOST memory, uint64 [H]: word h = host_seq << 32 | ran_out << 31 | cap_h
+  int32_t host_seq = 0;
+  int short_list = 0;        // the lists are SHORTER than min(L, H*base): bit 31 of the mirror words reports a head whose list ran out
+  int unsorted = 0;          // 1: `scores` are the un-sorted rows [H][scores_stride] of length Lrow and no list is given
+  void* list_ws = nullptr;    // optional: H * roundup(L,8) * 2 bytes, 16-B aligned - the looked-up lists travel through it
+  void* ws = nullptr;         // 1024 B ratios + 2 * H*256 int32
+  unsigned long long* trace = nullptr; // debug: phase timestamps of the one-launch budget kernel (may be null)
 };
 
 struct MergeParams {         // LOOK-M pivot merge (pkv_merge.hip)
-  const void* kptr;
-  const void* vptr;
-  const int32_t* idx;        // [B*H][idx_stride] selected past tokens (top-k order)
-  int64_t idx_stride;
-  void* k_out;               // [B,H,k+w,D]  rows ordered [window, selected]
-  void* v_out;               // [B,H,k+w,D]  rows ordered [selected, window]
-  int B, H, S, w, k, G;
-  int64_t ks_b, ks_h, ks_s;
-  int64_t vs_b, vs_h, vs_s;
-  uint8_t* mask;             // [S] 1 = selected by some (b,h)
-  int32_t* ndrop;            // number of dropped positions
-  int32_t* drop;             // [S] dropped positions, ascending
-  int32_t* pivot;            // [B*H][S] kept-row number (KEY order) every dropped row merges into
-  void* tn;                  // [B*H][ntp][D] unit-norm kept keys
-  int ntp;
-  int D;                     // head size: 64, 128 or 256
-  int32_t* kept_bad;         // [B*H] != 0: a kept key of the head has no finite unit-norm form (zeroed with the mask)
-  int32_t* bstart;           // [B*H][k+w+1] first entry of every kept row's group in blist (last = number of dropped rows)
-  int32_t* blist;            // [B*H][S] dropped positions grouped by the kept row they merge into
+  const void* kptr = nullptr;
+  const void* vptr = nullptr;
+  const int32_t* idx = nullptr; // [B*H][idx_stride] selected past tokens (top-k order)
+  int64_t idx_stride = 0;
+  void* k_out = nullptr;      // [B,H,k+w,D]  rows ordered [window, selected]
+  void* v_out = nullptr;      // [B,H,k+w,D]  rows ordered [selected, window]
+  int B = 0, H = 0, S = 0, w = 0, k = 0, G = 0;
+  int64_t ks_b = 0, ks_h = 0, ks_s = 0;
+  int64_t vs_b = 0, vs_h = 0, vs_s = 0;
+  uint8_t* mask = nullptr;    // [S] 1 = selected by some (b,h)
+  int32_t* ndrop = nullptr;   // number of dropped positions
+  int32_t* drop = nullptr;    // [S] dropped positions, ascending
+  int32_t* pivot = nullptr;   // [B*H][S] kept-row number (KEY order) every dropped row merges into
+  void* tn = nullptr;         // [B*H][ntp][D] unit-norm kept keys
+  int ntp = 0;
+  int D = 0;                 // head size: 64, 128 or 256
+  int32_t* kept_bad = nullptr; // [B*H] != 0: a kept key of the head has no finite unit-norm form (zeroed with the mask)
+  int32_t* bstart = nullptr;  // [B*H][k+w+1] first entry of every kept row's group in blist (last = number of dropped rows)
+  int32_t* blist = nullptr;   // [B*H][S] dropped positions grouped by the kept row they merge into
 };
 
 struct FlattenParams {
-  const void* cache;
-  const void* state;
-  const int32_t* head_lens;
-  const int32_t* cu_klen;
-  void* out;
-  int H, row_bytes;
+  const void* cache = nullptr;
+  const void* state = nullptr;
+  const int32_t* head_lens = nullptr;
+  const int32_t* cu_klen = nullptr;
+  void* out = nullptr;
+  int H = 0, row_bytes = 0;
 };
 
 struct L2NormParams {        // key-norm scan of the L2Norm policy (pkv_l2norm.hip)
-  const void* kptr;          // [B, Hkv, S, D], element strides below
-  void* neg_out;             // [B*Hkv][Lp] model dtype: -norm (+0 for a zero norm, -inf for a NaN norm); Lp % 8 == 0, Lp >= S.
+  const void* kptr = nullptr; // [B, Hkv, S, D], element strides below
+  void* neg_out = nullptr;    // [B*Hkv][Lp] model dtype: -norm (+0 for a zero norm, -inf for a NaN norm); Lp % 8 == 0, Lp >= S.
                              // The padding S..Lp-1 is NOT neutral: it holds copies of row S-1's value, so whatever reads
                              // the row must mask by L = S (topk_kernel, topk_f32_kernel and sort_rows_kernel all do)
-  void* norm_out;            // [B*Hkv][S] model dtype: the norms themselves, or null
-  int B, Hkv, S, D, Lp;
-  int64_t ks_b, ks_h, ks_s;
-  int nblk;                  // row blocks per head (set by launch_l2norm)
-  int norm_vec;              // norm_out takes 16-byte stores (set by launch_l2norm)
+  void* norm_out = nullptr;   // [B*Hkv][S] model dtype: the norms themselves, or null
+  int B = 0, Hkv = 0, S = 0, D = 0, Lp = 0;
+  int64_t ks_b = 0, ks_h = 0, ks_s = 0;
+  int nblk = 0;              // row blocks per head (set by launch_l2norm)
+  int norm_vec = 0;          // norm_out takes 16-byte stores (set by launch_l2norm)
 };
 
 struct H2OParams {
-  const void* q;
-  const void* k;
-  float* rowstat;     // [B*H][S] c_row = -log2 sum_j exp(x_ij) of every query row
-  void* scores;
-  int64_t scores_stride;
-  int B, H, S, w, G;
-  int D;              // head size: 64, 128 or 256
-  int64_t qs_b, qs_h, qs_s;
-  int64_t ks_b, ks_h, ks_s;
-  int scale_mode;
-  float sqrt_d, rcp_sqrt_d;
+  const void* q = nullptr;
+  const void* k = nullptr;
+  float* rowstat = nullptr; // [B*H][S] c_row = -log2 sum_j exp(x_ij) of every query row
+  void* scores = nullptr;
+  int64_t scores_stride = 0;
+  int B = 0, H = 0, S = 0, w = 0, G = 0;
+  int D = 0;          // head size: 64, 128 or 256
+  int64_t qs_b = 0, qs_h = 0, qs_s = 0;
+  int64_t ks_b = 0, ks_h = 0, ks_s = 0;
+  int scale_mode = 0;
+  float sqrt_d = 0, rcp_sqrt_d = 0;
 };
 
 hipError_t launch_logits(int dtype, const LogitsParams& p, hipStream_t st);

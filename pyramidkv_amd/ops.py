@@ -532,13 +532,18 @@ def sort_rows(scores: torch.Tensor, want_values: bool = True):
     return si, sv
 
 
+def _ada_ws_bytes(H: int, fp32: bool = False) -> int:
+    """Scratch of the budget entry points (pkv_api.hip ada_ws_bytes): 1024 B of ratios + two (fp32 rows: four) 256-bin tables per head."""
+    return 1024 + (4 * H * 256 * 4 + 4 * H * 4 if fp32 else 2 * H * 256 * 4)
+
+
 def ada_budget(sorted_val: torch.Tensor, base_capacity: int, floor_ratio: float, normalize: bool) -> torch.Tensor:
     """pyramidkv_utils.py:709-719.  sorted_val [H,L] descending -> int32 head_capacity [H]."""
     _require_gpu(sorted_val)
     sorted_val = sorted_val.contiguous()
     H, L = sorted_val.shape
     cap = torch.empty(H, dtype=torch.int32, device=sorted_val.device)
-    nb = 1024 + 2 * H * 256 * 4
+    nb = _ada_ws_bytes(H)
     ws = torch.empty(nb, dtype=torch.uint8, device=sorted_val.device)
     with torch.cuda.device(sorted_val.device):
         N.check(N.lib.pkv_ada_budget(N.dtype_code(sorted_val.dtype), H, L, sorted_val.data_ptr(), base_capacity,
@@ -559,7 +564,7 @@ def ada_budget_topm(scores: torch.Tensor, top_idx: torch.Tensor, base_capacity: 
     dev = scores.device
     out = torch.empty(2 * H + 1 + H, dtype=torch.int32, device=dev)          # cap | head_lens | cu_klen (one allocation)
     cap, head_lens, cu = out[:H], out[H:2 * H], out[2 * H:]
-    nb = 1024 + 2 * H * 256 * 4
+    nb = _ada_ws_bytes(H)
     with torch.cuda.device(dev):
         ws = workspace(nb, dev)
         N.check(N.lib.pkv_ada_budget_topm(N.dtype_code(scores.dtype), H, L, M, scores.data_ptr(), scores.stride(0),
@@ -581,7 +586,7 @@ def ada_budget_rows(scores: torch.Tensor, base_capacity: int, floor_ratio: float
     dev = scores.device
     meta = torch.empty(4 * H + 1, dtype=torch.int32, device=dev)
     cap, head_lens, cu, cuh = meta[:H], meta[H:2 * H], meta[2 * H:3 * H + 1], meta[3 * H + 1:]
-    nb = 1024 + (4 if scores.dtype == torch.float32 else 2) * H * 256 * 4 + 4 * H * 4
+    nb = _ada_ws_bytes(H, scores.dtype == torch.float32)
     with torch.cuda.device(dev):
         ws = workspace(nb, dev)
         N.check(N.lib.pkv_ada_budget_rows(N.dtype_code(scores.dtype), H, L, scores.data_ptr(), scores.stride(0), base_capacity,
@@ -599,7 +604,7 @@ def ada_adaptive_lists(scores: torch.Tensor, top_idx: torch.Tensor, base_capacit
     Hl, L = scores.shape
     M = top_idx.shape[1]
     out = torch.empty(Hl, M, dtype=scores.dtype, device=scores.device)
-    nb = 1024 + 2 * Hl * 256 * 4
+    nb = _ada_ws_bytes(Hl)
     with torch.cuda.device(scores.device):
         ws = workspace(nb, scores.device)
         N.check(N.lib.pkv_ada_adaptive_lists(N.dtype_code(scores.dtype), Hl, L, M, scores.data_ptr(), scores.stride(0),
