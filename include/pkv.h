@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 204 /* 0.2.4: + pkv_l2norm_workspace_bytes, pkv_compress_l2norm, pkv_debug_sqrt, PKV_K_L2NORM; no struct layout change,
+#define PKV_VERSION 204 /* still 0.2.4: + pkv_think_workspace_bytes, pkv_think_prune (two symbols added within 0.2.4: no struct layout
+                           change, PKV_K_COUNT stays 9 - the ThinK kernels have no profiling class - so a host built against 204
+                           keeps working; a host that needs them checks for the symbols).
+                           0.2.4: + pkv_l2norm_workspace_bytes, pkv_compress_l2norm, pkv_debug_sqrt, PKV_K_L2NORM; no struct layout change,
                            but PKV_K_COUNT grows from 8 to 9: pkv_prof_read now writes 9 entries, so a host built against 203
                            with arrays of 8 must check pkv_version() (or be rebuilt) before it reads the profile.
                            0.2.3: + pkv_debug_merge_route, pkv_debug_unit_div; no layout change.
@@ -54,7 +57,7 @@ enum pkv_status {
 };
 
 /* PKV_F32: pkv_score_window, pkv_score_h2o, pkv_topk(_ws), pkv_gather_compact, pkv_gather_streaming, pkv_gather_flat,
- * pkv_compress, pkv_compress_h2o, pkv_compress_l2norm, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
+ * pkv_compress, pkv_compress_h2o, pkv_compress_l2norm, pkv_think_prune, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
  * pkv_update_flatten_view, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
  * pkv_ada_budget_topm, pkv_ada_adaptive_lists, pkv_ada_select) answers PKV_ERR_DTYPE / PKV_ERR_UNSUPPORTED. */
 enum pkv_dtype { PKV_BF16 = 0, PKV_F16 = 1, PKV_F32 = 2 };
@@ -177,6 +180,35 @@ PKV_API int pkv_compress_h2o(const pkv_desc* d, const void* q, const void* k, co
 PKV_API size_t pkv_l2norm_workspace_bytes(const pkv_desc* d);
 PKV_API int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k_out, void* v_out, int32_t* idx_out,
                         void* norm_out, void* ws, size_t ws_bytes, pkv_stream_t stream);
+
+/* ThinK key-channel pruning (pyramidkv_utils.py:13-26 key_pruner_query_driven, called from :390 SnapKVCluster.update_think): a
+ * second pass over the keys a compress call has compacted.  Every key channel gets a score, the n_prune channels of smallest
+ * score are dropped from all but the last `recent` keys.  Three launches on `stream` (channel-energy scan -> select -> channel
+ * compaction), no host synchronisation (the reference's boolean-mask index is a nonzero() with one).
+ *   energy of a channel over n rows = every element squared and the square rounded to d->dtype (torch.pow in the model dtype;
+ *     fp32: one rounded multiply) -> fp32 sum of the rounded squares (the order is the library's own and fixed: two calls give
+ *     the same bits) -> ONE correctly rounded fp32 division by n -> ONE round-to-nearest-even to d->dtype;
+ *   qe = energy over the last min(32, S) rows of q (the 32 is the reference's literal, :17), ke = energy over all n_rows rows
+ *     of kc, score = dtype(float(qe) * float(ke));
+ *   pruned = the n_prune channels first in (score ascending, channel index ascending); NaN scores rank behind +inf, by index
+ *     (`torch.topk(largest=False)` leaves equal scores to the backend).
+ * The descriptor supplies dtype, B, H, S, D and q_stride; kv_group must divide H and is otherwise ignored, window, topk, the
+ * pooling fields and k_stride / v_stride are not looked at.
+ *   q:             [B,H,S,D] through d->q_stride (the model's transposed view is taken as it is).
+ *   kc:            d->dtype [B,H,n_rows,D] contiguous, n_rows >= 1.
+ *   recent:        0 <= recent < n_rows; n_prune: 0 <= n_prune < D (the host's int(D * ratio)); PKV_ERR_SHAPE otherwise.
+ *   k_pruned_out:  d->dtype [B*H][n_rows - recent][D - n_prune] contiguous: the kept channels, ascending, of rows
+ *                  0 .. n_rows - recent - 1, bit copies.  Nothing outside these bytes is written.
+ *   keep_out:      uint8 [B*H][D], 1 = kept (the reference's ~mask).
+ *   keep_idx_out:  int32 [B*H][D - n_prune] ascending, may be NULL (then it lives in ws); 4-byte aligned.
+ *   stats_out:     d->dtype [B*H][3][D] = qe, ke, score; may be NULL.
+ *   q, kc, k_pruned_out, stats_out, ws: 16-byte aligned.  ws: pkv_think_workspace_bytes(d, n_rows) (0 = the descriptor or
+ *   n_rows is not one this entry point takes).
+ * The rows n_rows - recent .. n_rows - 1 keep all D channels: the caller's view kc[:, :, n_rows - recent:, :], no kernel. */
+PKV_API size_t pkv_think_workspace_bytes(const pkv_desc* d, int32_t n_rows);
+PKV_API int pkv_think_prune(const pkv_desc* d, const void* q, const void* kc, int32_t n_rows, int32_t recent, int32_t n_prune,
+                    void* k_pruned_out, uint8_t* keep_out, int32_t* keep_idx_out /* may be NULL */,
+                    void* stats_out /* may be NULL */, void* ws, size_t ws_bytes, pkv_stream_t stream);
 
 /* Selection only: the front half of pkv_compress / pkv_compress_h2o (score -> top-k), idx_out int32 [B*H][d->topk].
  * What a caller needs when something other than the plain gather follows (the merge below).  ws: pkv_workspace_bytes(d). */

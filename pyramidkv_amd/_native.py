@@ -22,6 +22,12 @@ TIE = {"canonical": 0, "aten_rocm": 1}
 KERNEL_NAMES = ["logits", "finalize", "topk", "gather", "h2o_stats", "h2o_colsum", "sort", "budget", "l2norm"]
 
 
+# ThinK (csrc/pkv_kernels.hpp, same names): key rows per workgroup of the channel-energy scan = per fp32 partial, input bytes per
+# workgroup of the channel compaction (THINK_TILE_BYTES // (D * element size) rows), the reference's 32 query rows
+THINK_SCAN_ROWS = 128
+THINK_TILE_BYTES = 16384
+THINK_QROWS = 32
+
 PKV_VERSION = 204            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
 
 
@@ -80,6 +86,8 @@ def _load():
         "pkv_select": (C.c_int, [dp, vp, vp, i32, vp, vp, sz, vp]),
         "pkv_l2norm_workspace_bytes": (sz, [dp]),
         "pkv_compress_l2norm": (C.c_int, [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+        "pkv_think_workspace_bytes": (sz, [dp, i32]),
+        "pkv_think_prune": (C.c_int, [dp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
         "pkv_merge_workspace_bytes": (sz, [dp]),
         "pkv_merge_compact": (C.c_int, [dp, vp, vp, vp, i64, vp, vp, vp, sz, vp]),
         "pkv_sort_rows": (C.c_int, [i32, i32, i32, vp, i64, vp, vp, vp]),

@@ -9,6 +9,9 @@ is a plain container with the same methods the reference's forwards call (``upda
 ``__len__``, ``__getitem__``, ``to_legacy_cache``, ``from_legacy_cache``) plus the three the transformers-5 model
 forward asks every cache for (``is_sliding``, ``get_query_offset``, ``get_mask_sizes``).  No nvtx ranges
 (reference :63-69).
+
+``ThinKCache`` is the per-layer container of the ThinK forward (reference cache_utils_think.py:296, :390-431): pruned keys,
+full-width recent keys, the channel mask and the values.
 """
 from __future__ import annotations
 
@@ -84,3 +87,64 @@ class DynamicCacheSplitHeadFlatten:
                 k, v = past_key_values[layer_idx]
                 cache.update(k, v, layer_idx)
         return cache
+
+
+class ThinKCache:
+    """What the reference's vendored ``DynamicCache`` keeps for ThinK (cache_utils_think.py:296-312, ``update_think`` :390-424,
+    ``get_seq_length`` :426-431), as a plain container for the same reason as above.  Per layer:
+
+      key_cache_pruned  [1, H, R, D - n_prune]   the kept channels of the first R compacted keys
+      key_cache         [1, H, recent + t, D]    the recent keys and every key appended since, all D channels
+      mask              bool [1, H, D]           True = kept channel (the reference's ``~mask``)
+      value_cache       [1, H, R + recent + t, D]
+
+    ``keep_idx`` (int64 [1, H, D - n_prune], ascending) is derived from the mask once per layer, without a host
+    synchronisation: the decode step gathers the query's kept channels through it.  A layer that was not pruned (a prompt
+    shorter than the budget, or a merge: ``update_think`` returned the 2-tuple) is stored with zero pruned rows, all channels
+    kept and every key in ``key_cache``.  Batch 1, as in the reference."""
+    is_sliding = [False]
+
+    def __init__(self) -> None:
+        self.key_cache_pruned: List[torch.Tensor] = []
+        self.key_cache: List[torch.Tensor] = []
+        self.mask: List[torch.Tensor] = []
+        self.keep_idx: List[torch.Tensor] = []
+        self.value_cache: List[torch.Tensor] = []
+        self._seen_tokens = 0     # tokens of the sequence so far; the patched forward keeps it (llama_model_think.py:172)
+
+    def __len__(self):
+        return len(self.key_cache)
+
+    def update_think(self, key_states_pruned, key_states, mask, value_states, layer_idx, cache_kwargs=None):
+        """Stores a layer once (:419-424); a second call for the same layer is ignored, as there."""
+        if len(self.key_cache) <= layer_idx:
+            if len(self.key_cache) != layer_idx:
+                raise IndexError(f"ThinKCache holds {len(self.key_cache)} layers, layer {layer_idx} cannot be stored yet")
+            b, h, d = mask.shape
+            w = key_states_pruned.shape[-1]
+            self.key_cache_pruned.append(key_states_pruned.view(b, h, -1, w))
+            self.mask.append(mask)
+            # kept channels first, in ascending order (a stable sort of a 0/1 row): no nonzero(), no synchronisation
+            self.keep_idx.append(torch.sort(mask.to(torch.uint8), dim=-1, descending=True, stable=True).indices[..., :w])
+            self.key_cache.append(key_states)
+            self.value_cache.append(value_states)
+
+    def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
+        """Decode: append to the full-width recent part and to the values (:385-388)."""
+        self.key_cache[layer_idx] = torch.cat([self.key_cache[layer_idx], key_states], dim=-2)
+        self.value_cache[layer_idx] = torch.cat([self.value_cache[layer_idx], value_states], dim=-2)
+        return self.key_cache[layer_idx], self.value_cache[layer_idx]
+
+    def get_seq_length(self, layer_idx: Optional[int] = 0) -> int:
+        if len(self.key_cache) <= layer_idx:
+            return 0
+        return self.key_cache[layer_idx].shape[-2] + self.key_cache_pruned[layer_idx].shape[-2]      # :431
+
+    def get_query_offset(self, layer_idx: int = 0) -> int:
+        return self._seen_tokens if len(self.key_cache) > layer_idx else 0
+
+    def get_mask_sizes(self, query_length: int, layer_idx: int = 0):
+        return self.get_query_offset(layer_idx) + query_length, 0
+
+    def get_max_length(self) -> Optional[int]:
+        return None

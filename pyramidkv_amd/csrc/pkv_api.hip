@@ -138,27 +138,30 @@ enum DescNeed : unsigned {
                    // PKV_ERR_UNSUPPORTED for fp32 tensors
   L2NORM = 8,      // pkv_compress_l2norm alone: window must be 0 (everywhere else it is >= 1), S >= 1, topk <= S; q strides and
                    // the pooling fields are not looked at
+  THINK = 16,      // pkv_think_prune alone: a query tensor and nothing else of the prompt.  S >= 1; window, topk and the pooling
+                   // fields are not looked at; of the strides only q's (the keys it reads are contiguous by contract)
 };
 int check_desc(const pkv_desc* d, unsigned need) {
-  const bool l2 = need & L2NORM, need_topk = need & NEED_TOPK;
+  const bool l2 = need & L2NORM, th = need & THINK, need_topk = need & NEED_TOPK;
   if (!d) return PKV_ERR_NULL;
   if (d->dtype != PKV_BF16 && d->dtype != PKV_F16 && d->dtype != PKV_F32) return PKV_ERR_DTYPE;
   if (d->D != 64 && d->D != 128 && d->D != 256) return PKV_ERR_SHAPE;
   if (d->dtype == PKV_F32 && !(need & F32_OK)) return PKV_ERR_UNSUPPORTED;
-  if (d->B < 1 || d->H < 1 || d->S < (l2 ? 1 : 2)) return PKV_ERR_SHAPE;
+  if (d->B < 1 || d->H < 1 || d->S < (l2 || th ? 1 : 2)) return PKV_ERR_SHAPE;
   if (d->kv_group < 1 || d->H % d->kv_group) return PKV_ERR_SHAPE;
-  if (l2 ? d->window != 0 : d->window < 1 || d->window >= d->S) return PKV_ERR_SHAPE;
+  if (!th && (l2 ? d->window != 0 : d->window < 1 || d->window >= d->S)) return PKV_ERR_SHAPE;
   if ((need & SCORING) && (d->window > 128 || d->kv_group * d->window > 256)) return PKV_ERR_UNSUPPORTED;
   if (need_topk && (d->topk < 1 || d->topk > d->S - d->window)) return PKV_ERR_SHAPE;
-  if (!l2 && (d->pool_kind < 0 || d->pool_kind > 2)) return PKV_ERR_SHAPE;
+  const bool pooled = !l2 && !th;
+  if (pooled && (d->pool_kind < 0 || d->pool_kind > 2)) return PKV_ERR_SHAPE;
   if (d->tie_order != PKV_TIE_CANONICAL && d->tie_order != PKV_TIE_ATEN_ROCM) return PKV_ERR_SHAPE;
-  if (!l2 && d->pool_kind != PKV_POOL_NONE) {
+  if (pooled && d->pool_kind != PKV_POOL_NONE) {
     if (d->pool_kernel < 1 || !(d->pool_kernel & 1)) return PKV_ERR_SHAPE;
     if (d->pool_kernel > 17) return PKV_ERR_UNSUPPORTED;
   }
   const int64_t amask = d->dtype == PKV_F32 ? 3 : 7;                       // rows start on 16-byte boundaries
   for (int i = 0; i < 3; ++i)
-    if ((!l2 && (d->q_stride[i] & amask)) || (d->k_stride[i] & amask) || (d->v_stride[i] & amask)) return PKV_ERR_ALIGN;
+    if ((!l2 && (d->q_stride[i] & amask)) || (!th && ((d->k_stride[i] & amask) || (d->v_stride[i] & amask)))) return PKV_ERR_ALIGN;
   if ((int64_t)d->B * d->H > 65535) return PKV_ERR_UNSUPPORTED;
   if (d->dtype == PKV_F32 && need_topk && d->topk > topk_f32_max_k()) return PKV_ERR_UNSUPPORTED;
   return PKV_OK;
@@ -669,6 +672,54 @@ int pkv_compress_l2norm(const pkv_desc* d, const void* k, const void* v, void* k
   GatherParams g = make_gather(d, k, v, k_out, v_out);      // w = 0: L = S, no window rows behind the selected ones
   g.idx = fin; g.idx_stride = cap;
   return do_gather(g, cap, st);
+}
+
+// ---- ThinK key-channel pruning (pyramidkv_utils.py:13-26, :390): channel-energy scan -> select -> channel compaction ----
+namespace {
+struct ThinkWs { int nck; size_t off_part, off_idx, total; };
+ThinkWs think_ws(const pkv_desc* d, int n_rows) {
+  ThinkWs w;
+  const size_t BH = (size_t)d->B * d->H;
+  w.nck = (n_rows + THINK_SCAN_ROWS - 1) / THINK_SCAN_ROWS;
+  size_t o = 0;
+  w.off_part = o; o = align_up(o + BH * (w.nck + 1) * d->D * sizeof(float), 256);     // per-chunk sums, then the query rows'
+  w.off_idx = o;  o = align_up(o + BH * d->D * 4, 256);                                // keep_idx when the caller takes none
+  w.total = o;
+  return w;
+}
+}  // namespace
+
+size_t pkv_think_workspace_bytes(const pkv_desc* d, int32_t n_rows) {
+  PKV_LOAD_DESC(d, 0);
+  if (check_desc(d, THINK | F32_OK) || n_rows < 1) return 0;
+  return think_ws(d, n_rows).total;
+}
+
+int pkv_think_prune(const pkv_desc* d, const void* q, const void* kc, int32_t n_rows, int32_t recent, int32_t n_prune,
+                    void* k_pruned_out, uint8_t* keep_out, int32_t* keep_idx_out, void* stats_out, void* ws, size_t ws_bytes,
+                    pkv_stream_t stream) {
+  PKV_LOAD_DESC(d, rc_ld);
+  int rc = check_desc(d, THINK | F32_OK);
+  if (rc) return rc;
+  if (!q || !kc || !k_pruned_out || !keep_out || !ws) return PKV_ERR_NULL;
+  if (misaligned(q) || misaligned(kc) || misaligned(k_pruned_out) || misaligned(stats_out) || misaligned(ws) ||
+      (reinterpret_cast<uintptr_t>(keep_idx_out) & 3))
+    return PKV_ERR_ALIGN;
+  if (n_rows < 1 || recent < 0 || recent >= n_rows || n_prune < 0 || n_prune >= d->D) return PKV_ERR_SHAPE;
+  const ThinkWs W = think_ws(d, n_rows);
+  if (ws_bytes < W.total) return PKV_ERR_WORKSPACE;
+  char* w = static_cast<char*>(ws);
+  ThinkParams p;
+  p.q = q; p.kc = kc;
+  p.part = reinterpret_cast<float*>(w + W.off_part);
+  p.k_out = k_pruned_out; p.keep = keep_out;
+  p.keep_idx = keep_idx_out ? keep_idx_out : reinterpret_cast<int32_t*>(w + W.off_idx);
+  p.stats = stats_out;
+  p.B = d->B; p.H = d->H; p.S = d->S; p.D = d->D;
+  p.N = n_rows; p.R = n_rows - recent; p.nprune = n_prune;
+  p.nq = std::min(THINK_QROWS, d->S); p.nck = W.nck;
+  p.qs_b = d->q_stride[0]; p.qs_h = d->q_stride[1]; p.qs_s = d->q_stride[2];
+  return hip_rc(launch_think(d->dtype, p, static_cast<hipStream_t>(stream)));
 }
 
 namespace {

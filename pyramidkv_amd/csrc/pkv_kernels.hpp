@@ -277,6 +277,26 @@ struct L2NormParams {        // key-norm scan of the L2Norm policy (pkv_l2norm.h
   int norm_vec = 0;          // norm_out takes 16-byte stores (set by launch_l2norm)
 };
 
+// ThinK key-channel pruning (pkv_think.hip).  The two sizes below fix the order of every fp32 sum and the shape of every
+// output span; they depend on nothing but the tensor shape (pyramidkv_amd/_native.py mirrors them for the tests).
+constexpr int THINK_SCAN_ROWS = 128;      // key rows per workgroup of think_scan_kernel = per fp32 partial
+constexpr int THINK_TILE_BYTES = 16384;   // input bytes per workgroup of think_compact_kernel (16384 / (D * e) rows)
+constexpr int THINK_QROWS = 32;           // the reference's literal: q_states[..., -32:, :] (pyramidkv_utils.py:17)
+struct ThinkParams {
+  const void* q = nullptr;    // [B, H, S, D], element strides below
+  const void* kc = nullptr;   // [B, H, N, D] contiguous: the compacted keys
+  float* part = nullptr;      // [B*H][nck + 1][D] fp32 sums of rounded squares: nck key chunks, then the query rows
+  void* k_out = nullptr;      // [B*H][R][D - nprune] contiguous
+  uint8_t* keep = nullptr;    // [B*H][D] 1 = kept
+  int32_t* keep_idx = nullptr; // [B*H][D - nprune] ascending
+  void* stats = nullptr;      // [B*H][3][D] model dtype (qe, ke, score) or null
+  int B = 0, H = 0, S = 0, D = 0;
+  int N = 0, R = 0;           // rows of kc; R = N - recent rows are compacted
+  int nprune = 0, nq = 0;     // nq = min(THINK_QROWS, S)
+  int nck = 0;                // ceil(N / THINK_SCAN_ROWS)
+  int64_t qs_b = 0, qs_h = 0, qs_s = 0;
+};
+
 struct H2OParams {
   const void* q = nullptr;
   const void* k = nullptr;
@@ -323,6 +343,7 @@ size_t merge_max_seq();      // longest sequence the merge takes (LDS bitmap of 
 hipError_t launch_l2norm(int dtype, const L2NormParams& p, hipStream_t st);
 // dst [BH][n] = src row bh / G (stride src_stride), entries 0..n-1
 hipError_t launch_idx_expand(const int32_t* src, int64_t src_stride, int32_t* dst, int BH, int n, int G, hipStream_t st);
+hipError_t launch_think(int dtype, const ThinkParams& p, hipStream_t st);      // scan -> select -> compaction, three launches
 hipError_t launch_debug_sqrt(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_exp(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_round(int dtype, const float* in, uint16_t* out, int64_t n, hipStream_t st);

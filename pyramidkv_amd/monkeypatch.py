@@ -17,7 +17,8 @@ As in the reference the cache stores all H (query) heads, because K/V are expand
 ``pyramidkv_amd.DynamicCacheSplitHeadFlatten()`` as ``past_key_values`` (batch 1, as the reference); the decode step
 appends through ``pkv_update_flatten_view`` and attends per head over its own rows - the reference calls
 ``flash_attn_varlen_func`` there, this adapter uses a padded-batch softmax written in plain PyTorch ops (caller-side
-glue, like the rest of this file).
+glue, like the rest of this file).  ``think`` (reference llama_model_think.py) keeps pruned keys next to full-width recent
+ones: pass a ``pyramidkv_amd.ThinKCache()`` (batch 1); its decode step is plain PyTorch as well.
 """
 from __future__ import annotations
 
@@ -37,6 +38,8 @@ _METHODS: Dict[str, tuple] = {
     "l2norm": ("init_l2norm_native", False),      # reference monkeypatch.py:60-64,124-128; init_l2norm itself is a pinned placeholder
 }
 _FLAT_METHODS: Dict[str, str] = {"adakv": "init_adakv", "headkv": "init_headkv"}
+# reference monkeypatch.py (llama_model_think.py): update_think into a ThinKCache; init_think itself is a pinned placeholder
+_THINK_METHODS: Dict[str, str] = {"think": "init_think_native"}
 # the module whose init_* functions build the clusters; tests swap in an oracle-backed stand-in on CPU
 _cluster_module = _utils
 # hand K/V to update_kv BEFORE repeat_kv when the cluster accepts it (pyramidkv_amd's do); False = the reference's order
@@ -158,6 +161,56 @@ def _make_forward(method: str, apply_rotary_pos_emb: Callable):
     return forward
 
 
+def _make_think_forward(apply_rotary_pos_emb: Callable):
+    """ThinK (reference llama_model_think.py:87-216): prefill calls ``kv_cluster.update_think`` into a
+    ``pyramidkv_amd.ThinKCache``; a decode step scores the pruned keys with the query's kept channels only."""
+    init_name = _THINK_METHODS["think"]
+
+    def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
+        input_shape = hidden_states.shape[:-1]
+        hidden_shape = (*input_shape, -1, self.head_dim)
+        q = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+        k = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+        v = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+        cos, sin = position_embeddings
+        q, k = apply_rotary_pos_emb(q, k, cos, sin)
+        if past_key_values is not None and not hasattr(past_key_values, "key_cache_pruned"):
+            raise TypeError("think keeps pruned and full-width keys per layer: pass past_key_values=pyramidkv_amd.ThinKCache()")
+        if past_key_values is None or past_key_values.get_seq_length(self.layer_idx) == 0:      # prefill (:167-170)
+            if past_key_values is not None:
+                assert q.shape[0] == 1, "ThinK cache: batch 1 (reference llama_model_think.py:177)"
+                getattr(_cluster_module, init_name)(self)
+                if not (skip_repeat_kv and getattr(self.kv_cluster, "accepts_unexpanded_kv", False)):
+                    k = _repeat_kv(k, self.num_key_value_groups)          # :160-161
+                    v = _repeat_kv(v, self.num_key_value_groups)
+                out = self.kv_cluster.update_think(k, q, v, attention_mask, self.num_key_value_groups)   # :169
+                if len(out) == 2:             # a short prompt or a merge (pyramidkv_utils.py:357-358, :380-382): an unpruned layer
+                    kc, vc = out
+                    keep = torch.ones(kc.shape[0], kc.shape[1], kc.shape[3], dtype=torch.bool, device=kc.device)
+                    out = (kc[:, :, :0, :], kc, keep, vc)
+                past_key_values.update_think(*out, self.layer_idx)       # :170
+                _track_tokens(past_key_values, self.layer_idx, q.shape[-2], True)
+                past_key_values._seen_tokens = past_key_values._pkv_seen_tokens               # :172
+            attn = _attend(self, q, k, v, attention_mask, True)          # the prompt attends to the full K/V (:183)
+        else:                                                             # decode (:171-182, :185-195)
+            assert q.shape[0] == 1 and q.shape[-2] == 1, "ThinK decode: one token, batch 1"
+            k = _repeat_kv(k, self.num_key_value_groups)
+            v = _repeat_kv(v, self.num_key_value_groups)
+            kr, vv = past_key_values.update(k, v, self.layer_idx)        # :173
+            _track_tokens(past_key_values, self.layer_idx, 1, False)
+            past_key_values._seen_tokens = past_key_values._pkv_seen_tokens
+            kp = past_key_values.key_cache_pruned[self.layer_idx]
+            qp = q.gather(-1, past_key_values.keep_idx[self.layer_idx].unsqueeze(2))                # the query's kept channels (:177-178)
+            w = torch.cat([torch.matmul(qp, kp.transpose(2, 3)), torch.matmul(q, kr.transpose(2, 3))], dim=-1) * self.scaling
+            w = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)    # :193
+            attn = torch.matmul(w, vv).transpose(1, 2).contiguous()
+        attn = attn.reshape(*input_shape, -1).contiguous()
+        return self.o_proj(attn), None
+
+    forward.__name__ = "attn_forward_think"
+    return forward
+
+
 def varlen_decode_attention(q, k_flat, v_flat, cu_klen, max_seqlen_k, scaling):
     """One query token per head over a flat var-len cache: q [H, D], k_flat/v_flat [sum_h len_h, D], head h owns rows
     cu_klen[h]..cu_klen[h+1].  What flash_attn_varlen_func(..., cu_seqlens_q=arange(H+1), cu_seqlens_k=cu_klen,
@@ -222,14 +275,17 @@ def _make_flat_forward(method: str, apply_rotary_pos_emb: Callable):
 
 
 def _replace(module_path: str, class_name: str, method: str):
-    if method not in _METHODS and method not in _FLAT_METHODS:
+    if method not in _METHODS and method not in _FLAT_METHODS and method not in _THINK_METHODS:
         raise ValueError(f"method {method!r} is not wired in pyramidkv_amd.monkeypatch "
-                         f"(supported: {sorted(list(_METHODS) + list(_FLAT_METHODS))})")
+                         f"(supported: {sorted(list(_METHODS) + list(_FLAT_METHODS) + list(_THINK_METHODS))})")
     import importlib
     mod = importlib.import_module(module_path)
     cls = getattr(mod, class_name)
     if not hasattr(cls, "_pkv_original_forward"):
         cls._pkv_original_forward = cls.forward
+    if method in _THINK_METHODS:
+        cls.forward = _make_think_forward(mod.apply_rotary_pos_emb)
+        return
     make = _make_flat_forward if method in _FLAT_METHODS else _make_forward
     cls.forward = make(method, mod.apply_rotary_pos_emb)
 

@@ -317,6 +317,47 @@ def compress_l2norm(k, v, cap: int, kv_group: int = 1, idx_out: Optional[torch.T
     return out
 
 
+def think_prune(q, kc, recent: int, n_prune: int, return_keep_idx: bool = False, return_stats: bool = False,
+                out: Optional[torch.Tensor] = None):
+    """ThinK key-channel pruning (pyramidkv_utils.py:13-26 key_pruner_query_driven) in one C call on the current stream:
+    channel-energy scan -> select -> channel compaction, no host synchronisation.  q: [B,H,S,D] (any strides that keep rows
+    16-byte aligned: the model's transposed view goes in as it is), kc: [B,H,N,D] compacted keys, 0 <= recent < N,
+    0 <= n_prune < D.  Returns (k_pruned [1, B*H, N-recent, D-n_prune], keep bool [B,H,D]), then keep_idx int32
+    [B,H,D-n_prune] (ascending) with ``return_keep_idx`` and stats [B,H,3,D] = (qe, ke, score) in the model dtype with
+    ``return_stats``.  ``out``: a contiguous tensor of B*H*(N-recent)*(D-n_prune) elements that receives k_pruned (16-byte
+    aligned; nothing outside it is written)."""
+    _require_gpu(q, kc)
+    if q.dim() != 4 or kc.dim() != 4 or q.shape[:2] != kc.shape[:2] or q.shape[3] != kc.shape[3] or q.dtype != kc.dtype:
+        raise ValueError(f"think_prune: q {tuple(q.shape)} {q.dtype} and kc {tuple(kc.shape)} {kc.dtype} do not belong together")
+    q, kc = _rowmajor(q), kc.contiguous()
+    B, H, n_rows, D = kc.shape
+    R, W = n_rows - recent, D - n_prune
+    with _DeviceGuard(kc.device):
+        d = make_desc(q, q, None, 0, num_heads=H)
+        nb = N.lib.pkv_think_workspace_bytes(d, n_rows)
+        ws, st = _workspace_and_stream(max(nb, 1), kc.device)       # nb == 0: the call below names what is wrong
+        if out is not None:
+            if out.dtype != kc.dtype or not out.is_contiguous() or out.numel() != B * H * max(R, 0) * max(W, 0):
+                raise ValueError("out must be a contiguous tensor of B*H*(N-recent)*(D-n_prune) elements of the keys' dtype")
+            kp = out
+        else:
+            kp = torch.empty(1, B * H, max(R, 0), max(W, 0), dtype=kc.dtype, device=kc.device)
+        keep = torch.empty(B, H, D, dtype=torch.bool, device=kc.device)
+        kidx = torch.empty(B, H, max(W, 0), dtype=torch.int32, device=kc.device) if return_keep_idx else None
+        stats = torch.empty(B, H, 3, D, dtype=kc.dtype, device=kc.device) if return_stats else None
+        rc = N.lib.pkv_think_prune(d, q.data_ptr(), kc.data_ptr(), n_rows, recent, n_prune, kp.data_ptr(), keep.data_ptr(),
+                                   kidx.data_ptr() if kidx is not None else None,
+                                   stats.data_ptr() if stats is not None else None, ws.data_ptr(), ws.numel(), st)
+        if rc:
+            N.check(rc, "pkv_think_prune")
+    res = (kp.view(1, B * H, R, W), keep)
+    if return_keep_idx:
+        res += (kidx,)
+    if return_stats:
+        res += (stats,)
+    return res
+
+
 # ---- prepared calls (round 5): everything of one update_kv that does not change from call to call ----------------------
 # At S <= 8192 one dense update_kv is bound by the HOST's time to issue it (bench.py `sweep[].host_us`).  A cluster therefore
 # keeps, per (shapes, strides, dtype, device, budget, knobs), the filled descriptor, its byref object, the scratch size and the

@@ -24,7 +24,7 @@ import torch
 
 from . import ops
 from . import config as _cfg
-from .cache import DynamicCacheSplitHeadFlatten  # noqa: F401  (llama_model.py:20 / mistral_model.py:20 import it from here)
+from .cache import DynamicCacheSplitHeadFlatten, ThinKCache  # noqa: F401  (llama_model.py:20 / mistral_model.py:20 import the first from here)
 
 
 def _check_merge(merge):
@@ -234,6 +234,30 @@ class SnapKVCluster(_WindowPolicy):
         _check_merge(self.merge)
         return self._compress(key_states, query_states, value_states,
                               self.max_capacity_prompt - self.window_size, num_key_value_groups)
+
+
+    def update_think(self, key_states, query_states, value_states, attention_mask, num_key_value_groups):
+        """reference :349-391 (ThinK): ``update_kv``, then the key channels of lowest query-driven score are dropped from all
+        but the last ``recent_size`` compacted keys (ops.think_prune, same stream, no host synchronisation).  Returns
+        ``(k_pruned [1, B*H, cap - recent, D - n_prune], k_recent [B, H, recent, D] (a view), keep bool [B, H, D], V_c)``.
+
+        As in the reference a prompt shorter than ``max_capacity_prompt`` (:357-358) and a cluster with ``merge`` set
+        (:380-382) return exactly what ``update_kv`` returns, a 2-tuple: the caller tells the two forms apart by length.
+        ``recent_size >= max_capacity_prompt`` (the reference fails in ``reshape`` there) and a ``ratio`` whose
+        ``int(D * ratio)`` is negative or reaches D raise ValueError before anything is launched."""
+        assert key_states.shape[-2] == query_states.shape[-2]                       # :352
+        q_len, head_dim = query_states.shape[-2], query_states.shape[-1]
+        if q_len < self.max_capacity_prompt or self.merge is not None:              # :357, :380
+            return self.update_kv(key_states, query_states, value_states, attention_mask, num_key_value_groups)
+        n_prune = int(head_dim * self.ratio)                                        # :15
+        if not 0 <= n_prune < head_dim:
+            raise ValueError(f"ratio {self.ratio} prunes int({head_dim} * ratio) = {n_prune} key channels of {head_dim}: "
+                             "need 0 <= n_prune < head_dim")
+        if not 0 <= self.recent_size < self.max_capacity_prompt:
+            raise ValueError(f"recent_size {self.recent_size} must lie in [0, max_capacity_prompt = {self.max_capacity_prompt})")
+        kc, vc = self.update_kv(key_states, query_states, value_states, attention_mask, num_key_value_groups)
+        k_pruned, keep = ops.think_prune(query_states, kc, self.recent_size, n_prune)      # :390
+        return k_pruned, kc[:, :, kc.shape[2] - self.recent_size:, :], keep, vc
 
 
 class H2OKVCluster(_WindowPolicy):
@@ -896,6 +920,23 @@ def init_l2norm_native(self):
         _default(self.config, 'skip_layers', [0, 1])
     _rebuilt(self, L2NormCluster(max_capacity_prompt=self.config.max_capacity_prompt, layer_idx=self.layer_idx,
                                  skip_layers=self.config.skip_layers))
+
+
+def init_think_native(self):
+    """reference :926-952 (init_think: same defaults, cluster rebuilt on every call, as there).  ``init_think`` itself stays the
+    placeholder below - a test pins that it raises - so ``replace_llama("think")`` names this factory."""
+    if not hasattr(self, "kv_cluster"):
+        _default(self.config, 'window_size', 32)
+        _default(self.config, 'max_capacity_prompt', 4096)
+        _default(self.config, 'kernel_size', 5)
+        _default(self.config, 'pooling', 'avgpool')
+        _default(self.config, 'merge', None)
+        _default(self.config, 'recent_size', 32)
+        _default(self.config, 'ratio', 0.4)
+    _rebuilt(self, SnapKVCluster(
+        window_size=self.config.window_size, max_capacity_prompt=self.config.max_capacity_prompt,
+        kernel_size=self.config.kernel_size, pooling=self.config.pooling, merge=self.config.merge,
+        recent_size=self.config.recent_size, ratio=self.config.ratio))
 
 
 def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
