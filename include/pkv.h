@@ -26,7 +26,10 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 204 /* still 0.2.4: + pkv_think_workspace_bytes, pkv_think_prune (two symbols added within 0.2.4: no struct layout
+#define PKV_VERSION 204 /* still 0.2.4: + pkv_decode_attn_splits, pkv_decode_attn_workspace_bytes, pkv_decode_attn_flat (three more symbols
+                           added within 0.2.4, exactly as the ThinK ones below: no struct layout change, no profiling class, PKV_K_COUNT
+                           stays 9; a host that needs them checks for the symbols).
+                           + pkv_think_workspace_bytes, pkv_think_prune (two symbols added within 0.2.4: no struct layout
                            change, PKV_K_COUNT stays 9 - the ThinK kernels have no profiling class - so a host built against 204
                            keeps working; a host that needs them checks for the symbols).
                            0.2.4: + pkv_l2norm_workspace_bytes, pkv_compress_l2norm, pkv_debug_sqrt, PKV_K_L2NORM; no struct layout change,
@@ -58,7 +61,7 @@ enum pkv_status {
 
 /* PKV_F32: pkv_score_window, pkv_score_h2o, pkv_topk(_ws), pkv_gather_compact, pkv_gather_streaming, pkv_gather_flat,
  * pkv_compress, pkv_compress_h2o, pkv_compress_l2norm, pkv_think_prune, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
- * pkv_update_flatten_view, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
+ * pkv_update_flatten_view and pkv_decode_attn_flat, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
  * pkv_ada_budget_topm, pkv_ada_adaptive_lists, pkv_ada_select) answers PKV_ERR_DTYPE / PKV_ERR_UNSUPPORTED. */
 enum pkv_dtype { PKV_BF16 = 0, PKV_F16 = 1, PKV_F32 = 2 };
 enum pkv_pool { PKV_POOL_NONE = 0, PKV_POOL_AVG = 1, PKV_POOL_MAX = 2 };
@@ -319,6 +322,43 @@ PKV_API int pkv_gather_flat(const pkv_desc* d, const void* k, const void* v, con
 PKV_API int pkv_update_flatten_view(int32_t dtype, int32_t H, int32_t head_dim, const void* cache,
                             const void* state, const int32_t* head_lens, const int32_t* cu_klen,
                             void* out, pkv_stream_t stream);
+
+/* Decode-time attention over the flat cache (llama_model.py:2377-2388: flash_attn_varlen_func(q, k_flat, v_flat, cu_qlen,
+ * cu_klen, 1, max_seqlen_k, causal=True) at :2386, one query row per head; with one query row the causal mask hides
+ * nothing).  Head h owns rows a = cu_klen[h] .. cu_klen[h+1] of k_flat / v_flat, n_h of them:
+ *   s_j    = fp32(sum_d q[h,d] * k[a+j,d]) * scale     fp32 products and sums of the inputs as they are: no rounding to dtype
+ *   out[h] = dtype(sum_j softmax_fp32(s)_j * v[a+j])   fp32 accumulator, ONE correctly rounded fp32 division by the fp32 sum of
+ *                                                      the weights, ONE round-to-nearest-even to dtype; exp = the accurate one of
+ *                                                      the window scores (pkv_debug_exp)
+ *   lse[h] = max_j s_j + log(sum_j exp(s_j - max))     fp32 (the logarithm in fp64, rounded once)
+ * A head with n_h = 0 gets zeros and lse = -inf, never NaN (the library's definition).  The order of the fp32 sums is the
+ * library's own and a function of (head_dim, dtype, splits) and PKV_DECODE_CHUNK alone: two calls give the same bits, and
+ * neither max_seqlen_k nor the other heads' lengths change a head's bits at equal `splits`.
+ * Every head is walked in chunks of PKV_DECODE_CHUNK rows, chunk c belongs to split c % splits, the grid is (H, splits).
+ * splits == 1: one launch.  splits > 1: the first launch leaves fp32 partials (max, sum, accumulator[head_dim]) per (head, split)
+ * in ws, a second small launch merges them in split order (two launches, no hand-off between workgroups inside one).
+ *   q:             dtype [H] rows of head_dim elements, q_stride ELEMENTS between heads (>= head_dim, keeps rows 16-byte aligned)
+ *   k_flat/v_flat: dtype [sum_h n_h][head_dim] contiguous;  cu_klen: device int32 [H+1], non-decreasing
+ *   max_seqlen_k:  >= 1; only picks the default split count - a head longer than it is still attended in full
+ *   splits:        0 = pkv_decode_attn_splits(H, head_dim, max_seqlen_k), else 1 .. PKV_DECODE_MAX_SPLITS
+ *   out:           dtype [H][head_dim] contiguous;  lse_out: float [H], may be NULL
+ *   ws:            pkv_decode_attn_workspace_bytes(H, head_dim, splits) bytes (0 for splits == 1, ws may then be NULL)
+ * Nothing outside out, lse_out and ws is written.  q, k_flat, v_flat, out, ws: 16-byte aligned.
+ * PKV_ERR_DTYPE: dtype; PKV_ERR_SHAPE: H < 1, head_dim not in {64,128,256}, max_seqlen_k < 1, q_stride < head_dim, splits out of
+ * range, a scale that is not finite; PKV_ERR_NULL; PKV_ERR_ALIGN: a pointer or q_stride breaks 16-byte rows; PKV_ERR_WORKSPACE.
+ * All of them are answered before any HIP call.  Non-finite scores are outside the contract (a NaN score counts as -inf).
+ * pkv_decode_attn_splits is host-only and a pure function of its arguments (no device query): about four workgroups per CU
+ * of the 256-CU part, never more splits than ceil(max_seqlen_k / PKV_DECODE_CHUNK); >= 1, non-decreasing in max_seqlen_k;
+ * an argument <= 0 gives 0. */
+#define PKV_DECODE_CHUNK 128     /* rows per chunk: one batch of 16-byte loads of a 256-thread workgroup at 256-byte rows */
+#define PKV_DECODE_MAX_SPLITS 64
+PKV_API int pkv_decode_attn_splits(int32_t H, int32_t head_dim, int32_t max_seqlen_k);
+PKV_API size_t pkv_decode_attn_workspace_bytes(int32_t H, int32_t head_dim, int32_t splits);
+PKV_API int pkv_decode_attn_flat(int32_t dtype, int32_t H, int32_t head_dim, const void* q, int64_t q_stride /* elements between heads */,
+                                 const void* k_flat, const void* v_flat, const int32_t* cu_klen /* device int32 [H+1] */,
+                                 int32_t max_seqlen_k /* launch hint, >= 1 */, float scale, int32_t splits /* 0 = default */,
+                                 void* out /* dtype [H][head_dim] contiguous */, float* lse_out /* [H], may be NULL */,
+                                 void* ws, size_t ws_bytes, pkv_stream_t stream);
 
 /* ---- multi-GPU: the one exchange step of the head-sharded path (the reference has no
  * collective: run_longbench.py:390 only places layers with device_map="auto") ----

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <vector>
 
@@ -943,6 +944,60 @@ int pkv_update_flatten_view(int32_t dtype, int32_t H, int32_t head_dim, const vo
   fp.cache = cache; fp.state = state; fp.head_lens = head_lens; fp.cu_klen = cu_klen; fp.out = out;
   fp.H = H; fp.row_bytes = head_dim * (dtype == PKV_F32 ? 4 : 2);
   return hip_rc(launch_flatten(fp, static_cast<hipStream_t>(stream)));
+}
+
+// ---- single-query attention over the flat cache (llama_model.py:2377-2388): one launch, or partials + combine ----
+namespace {
+// the default split count: enough (head, split) workgroups for a few per CU of the gfx950 part, never more splits than the
+// longest head has chunks.  A pure function of its arguments (no device query): the same shape takes the same route - and
+// sums in the same order - on every host.  head_dim does not enter it yet.
+constexpr int DECODE_CUS = 256, DECODE_WGS_PER_CU = 4;
+int decode_splits(int H, int head_dim, int max_seqlen_k) {
+  if (H < 1 || head_dim < 1 || max_seqlen_k < 1) return 0;
+  const int chunks = (int)(((int64_t)max_seqlen_k + PKV_DECODE_CHUNK - 1) / PKV_DECODE_CHUNK);
+  const int want = std::max(1, DECODE_CUS * DECODE_WGS_PER_CU / H);
+  return std::min(std::min(chunks, want), PKV_DECODE_MAX_SPLITS);
+}
+struct DecodeWs { size_t off_ml, off_acc, total; };
+DecodeWs decode_ws(int H, int head_dim, int splits) {
+  DecodeWs w;
+  size_t o = 0;
+  w.off_ml = o;  o = align_up(o + (size_t)H * splits * 2 * sizeof(float), 256);
+  w.off_acc = o; o = align_up(o + (size_t)H * splits * head_dim * sizeof(float), 256);
+  w.total = o;
+  return w;
+}
+}  // namespace
+
+int pkv_decode_attn_splits(int32_t H, int32_t head_dim, int32_t max_seqlen_k) { return decode_splits(H, head_dim, max_seqlen_k); }
+
+size_t pkv_decode_attn_workspace_bytes(int32_t H, int32_t head_dim, int32_t splits) {
+  if (H < 1 || head_dim < 1 || splits <= 1 || splits > PKV_DECODE_MAX_SPLITS) return 0;
+  return decode_ws(H, head_dim, splits).total;
+}
+
+int pkv_decode_attn_flat(int32_t dtype, int32_t H, int32_t head_dim, const void* q, int64_t q_stride, const void* k_flat,
+                         const void* v_flat, const int32_t* cu_klen, int32_t max_seqlen_k, float scale, int32_t splits, void* out,
+                         float* lse_out, void* ws, size_t ws_bytes, pkv_stream_t stream) {
+  if (dtype != PKV_BF16 && dtype != PKV_F16 && dtype != PKV_F32) return PKV_ERR_DTYPE;
+  if (H < 1 || (head_dim != 64 && head_dim != 128 && head_dim != 256) || max_seqlen_k < 1 || q_stride < head_dim) return PKV_ERR_SHAPE;
+  if (splits < 0 || splits > PKV_DECODE_MAX_SPLITS || !std::isfinite(scale)) return PKV_ERR_SHAPE;
+  if (!q || !k_flat || !v_flat || !cu_klen || !out) return PKV_ERR_NULL;
+  if (splits == 0) splits = decode_splits(H, head_dim, max_seqlen_k);
+  if (splits > 1 && !ws) return PKV_ERR_NULL;
+  if (misaligned(q) || misaligned(k_flat) || misaligned(v_flat) || misaligned(out) || (q_stride & (dtype == PKV_F32 ? 3 : 7)) ||
+      (reinterpret_cast<uintptr_t>(cu_klen) & 3) || (reinterpret_cast<uintptr_t>(lse_out) & 3) || (splits > 1 && misaligned(ws)))
+    return PKV_ERR_ALIGN;
+  DecodeParams p;
+  if (splits > 1) {
+    const DecodeWs W = decode_ws(H, head_dim, splits);
+    if (ws_bytes < W.total) return PKV_ERR_WORKSPACE;
+    p.part_ml = reinterpret_cast<float*>(static_cast<char*>(ws) + W.off_ml);
+    p.part_acc = reinterpret_cast<float*>(static_cast<char*>(ws) + W.off_acc);
+  }
+  p.q = q; p.k = k_flat; p.v = v_flat; p.cu_klen = cu_klen; p.out = out; p.lse = lse_out;
+  p.H = H; p.D = head_dim; p.splits = splits; p.q_stride = q_stride; p.scale = scale;
+  return hip_rc(launch_decode_attn(dtype, p, static_cast<hipStream_t>(stream)));
 }
 
 /* ---- debug / test hooks (not part of the drop-in surface) ---- */

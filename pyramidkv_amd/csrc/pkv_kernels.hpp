@@ -297,6 +297,22 @@ struct ThinkParams {
   int64_t qs_b = 0, qs_h = 0, qs_s = 0;
 };
 
+// Single-query attention over the flat var-len cache (pkv_decode.hip).  The chunk length PKV_DECODE_CHUNK (include/pkv.h) and
+// `splits` fix the order of every fp32 sum.
+struct DecodeParams {
+  const void* q = nullptr;    // [H][q_stride] model dtype, head_dim elements used
+  const void* k = nullptr;    // [sum_h n_h][D] contiguous
+  const void* v = nullptr;
+  const int32_t* cu_klen = nullptr; // [H+1]
+  void* out = nullptr;        // [H][D] model dtype
+  float* lse = nullptr;       // [H] or null
+  float* part_ml = nullptr;   // splits > 1: [H][splits][2] (max, sum) of every (head, split) that holds a chunk
+  float* part_acc = nullptr;  // splits > 1: [H][splits][D] its un-normalised accumulator
+  int H = 0, D = 0, splits = 0;
+  int64_t q_stride = 0;
+  float scale = 0;
+};
+
 struct H2OParams {
   const void* q = nullptr;
   const void* k = nullptr;
@@ -344,6 +360,7 @@ hipError_t launch_l2norm(int dtype, const L2NormParams& p, hipStream_t st);
 // dst [BH][n] = src row bh / G (stride src_stride), entries 0..n-1
 hipError_t launch_idx_expand(const int32_t* src, int64_t src_stride, int32_t* dst, int BH, int n, int G, hipStream_t st);
 hipError_t launch_think(int dtype, const ThinkParams& p, hipStream_t st);      // scan -> select -> compaction, three launches
+hipError_t launch_decode_attn(int dtype, const DecodeParams& p, hipStream_t st);   // one launch; splits > 1: + the combine launch
 hipError_t launch_debug_sqrt(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_exp(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_round(int dtype, const float* in, uint16_t* out, int64_t n, hipStream_t st);

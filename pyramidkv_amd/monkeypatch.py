@@ -16,8 +16,8 @@ As in the reference the cache stores all H (query) heads, because K/V are expand
 (reference llama_model.py:2236-2391 / :2393-2540) keep a FLAT per-head var-len cache: pass a
 ``pyramidkv_amd.DynamicCacheSplitHeadFlatten()`` as ``past_key_values`` (batch 1, as the reference); the decode step
 appends through ``pkv_update_flatten_view`` and attends per head over its own rows - the reference calls
-``flash_attn_varlen_func`` there, this adapter uses a padded-batch softmax written in plain PyTorch ops (caller-side
-glue, like the rest of this file).  ``think`` (reference llama_model_think.py) keeps pruned keys next to full-width recent
+``flash_attn_varlen_func`` there, this adapter calls ``ops.decode_attn_flat`` (``pkv_decode_attn_flat``) on HIP tensors; the
+padded-batch softmax in plain PyTorch ops below, ``varlen_decode_attention``, serves CPU tensors (the plumbing tests).  ``think`` (reference llama_model_think.py) keeps pruned keys next to full-width recent
 ones: pass a ``pyramidkv_amd.ThinKCache()`` (batch 1); its decode step is plain PyTorch as well.
 """
 from __future__ import annotations
@@ -27,6 +27,7 @@ from typing import Callable, Dict
 import torch
 import torch.nn.functional as F
 
+from . import ops as _ops
 from . import pyramidkv_utils as _utils
 
 # method -> (init function name in pyramidkv_utils, takes num_hidden_layers)
@@ -44,6 +45,13 @@ _THINK_METHODS: Dict[str, str] = {"think": "init_think_native"}
 _cluster_module = _utils
 # hand K/V to update_kv BEFORE repeat_kv when the cluster accepts it (pyramidkv_amd's do); False = the reference's order
 skip_repeat_kv = True
+# the flat-cache decode step on HIP tensors: ops.decode_attn_flat (the native kernel); False = varlen_decode_attention, the eager
+# statement of the same attention (what CPU tensors always take)
+native_decode_attention = True
+
+
+def _is_hip(t: torch.Tensor) -> bool:
+    return t.is_cuda
 
 
 def _repeat_kv(x: torch.Tensor, n_rep: int) -> torch.Tensor:
@@ -265,7 +273,8 @@ def _make_flat_forward(method: str, apply_rotary_pos_emb: Callable):
             cl.head_lens += 1
             if self.layer_idx == 0:
                 past_key_values._seen_tokens += 1
-            out = varlen_decode_attention(q[0, :, 0], kf, vf, cl.cu_klen, cl.max_seqlen_k, self.scaling)   # [H, D]
+            attend = _ops.decode_attn_flat if native_decode_attention and _is_hip(kf) else varlen_decode_attention
+            out = attend(q[0, :, 0], kf, vf, cl.cu_klen, cl.max_seqlen_k, self.scaling)   # [H, D] (:2377-2388)
             attn = out[None, None]                                        # [1, 1, H, D]
         attn = attn.reshape(*input_shape, -1).contiguous()
         return self.o_proj(attn), None

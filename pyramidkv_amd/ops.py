@@ -725,3 +725,35 @@ def update_flatten_view(cache: torch.Tensor, state: torch.Tensor, head_lens: tor
                                               head_lens.data_ptr(), cu_klen.data_ptr(), out.data_ptr(),
                                               N.stream_ptr()), "pkv_update_flatten_view")
     return out
+
+
+def decode_attn_flat(q: torch.Tensor, k_flat: torch.Tensor, v_flat: torch.Tensor, cu_klen: torch.Tensor, max_seqlen_k: int,
+                     scaling: float, splits: Optional[int] = None, return_lse: bool = False):
+    """One query row per head over the flat var-len cache: what flash_attn_varlen_func(q, k_flat, v_flat, cu_qlen, cu_klen, 1,
+    max_seqlen_k, causal=True) computes at llama_model.py:2377-2388, in one C call on the current stream.  q: [H, D] with any
+    head stride that keeps rows 16-byte aligned, k_flat / v_flat: [sum_h n_h, D], cu_klen: int32 [H+1] on the device.
+    ``max_seqlen_k`` only picks the default split count; ``splits`` overrides it (1 .. PKV_DECODE_MAX_SPLITS).
+    Returns out [H, D] in q's dtype, then lse float32 [H] with ``return_lse``.  A head without rows gets zeros, lse = -inf."""
+    _require_gpu(q, k_flat, v_flat, cu_klen)
+    if cu_klen.dtype != torch.int32:
+        raise ValueError("expected cu_klen to be int32")
+    if q.dim() != 2 or k_flat.dim() != 2 or k_flat.shape != v_flat.shape or k_flat.shape[1] != q.shape[1] or \
+            not (q.dtype == k_flat.dtype == v_flat.dtype) or cu_klen.numel() != q.shape[0] + 1:
+        raise ValueError(f"decode_attn_flat: q {tuple(q.shape)} {q.dtype}, k_flat {tuple(k_flat.shape)} {k_flat.dtype}, v_flat "
+                         f"{tuple(v_flat.shape)} {v_flat.dtype} and cu_klen [{cu_klen.numel()}] do not belong together")
+    H, D = q.shape
+    code = N.dtype_code(q.dtype)
+    if q.stride(1) != 1 or (q.stride(0) * q.element_size()) % 16 or q.data_ptr() % 16:
+        q = q.contiguous()
+    k_flat, v_flat, cu_klen = k_flat.contiguous(), v_flat.contiguous(), cu_klen.contiguous()
+    sp = int(splits) if splits else N.lib.pkv_decode_attn_splits(H, D, int(max_seqlen_k))
+    with _DeviceGuard(q.device):
+        ws, st = _workspace_and_stream(max(N.lib.pkv_decode_attn_workspace_bytes(H, D, sp), 1), q.device)
+        out = torch.empty(H, D, dtype=q.dtype, device=q.device)
+        lse = torch.empty(H, dtype=torch.float32, device=q.device) if return_lse else None
+        rc = N.lib.pkv_decode_attn_flat(code, H, D, q.data_ptr(), q.stride(0), k_flat.data_ptr(), v_flat.data_ptr(), cu_klen.data_ptr(),
+                                        int(max_seqlen_k), float(scaling), sp, out.data_ptr(),
+                                        lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(), st)
+        if rc:
+            N.check(rc, "pkv_decode_attn_flat")
+    return (out, lse) if return_lse else out
