@@ -26,7 +26,9 @@
 extern "C" {
 #endif
 
-#define PKV_VERSION 204 /* still 0.2.4: + pkv_decode_attn_splits, pkv_decode_attn_workspace_bytes, pkv_decode_attn_flat (three more symbols
+#define PKV_VERSION 204 /* still 0.2.4: + pkv_debug_h2o_route, pkv_debug_h2o_rows (two debug hooks added within 0.2.4: no struct layout
+                           change, no workspace change; the release library answers PKV_ERR_UNSUPPORTED).
+                           + pkv_decode_attn_splits, pkv_decode_attn_workspace_bytes, pkv_decode_attn_flat (three more symbols
                            added within 0.2.4, exactly as the ThinK ones below: no struct layout change, no profiling class, PKV_K_COUNT
                            stays 9; a host that needs them checks for the symbols).
                            + pkv_think_workspace_bytes, pkv_think_prune (two symbols added within 0.2.4: no struct layout
@@ -411,6 +413,20 @@ PKV_API int pkv_debug_score_route(int32_t* out, int n);
  *   more than one range, 11 scatter group of 0 rows, 12 of more than 2048 rows, 13 / 14 a 64-row block with a tail of 1..31 /
  *   33..63 rows, 15 a row whose maximum is zero was looked at again.  Words that do not apply are 0. */
 PKV_API int pkv_debug_merge_route(int32_t* out, int n);
+/* Route record of the last bf16 / fp16 H2O score call on this library (pkv_score_h2o, pkv_compress_h2o, pkv_select with h2o;
+ * debug build; the release library answers PKV_ERR_UNSUPPORTED).  The fp32 form records nothing: after an fp32 call both hooks
+ * still answer for the last 16-bit one.  Waits for the device, then copies min(n, 16) int32 words to `out`:
+ *   0 dtype   1 KS (MFMA k-steps: head_dim / 32)   2, 3 grid of h2o_stats_kernel (x = 256-row workgroups per head, y = B*H)
+ *   4, 5 grid of h2o_colsum_kernel   6 ntiles (64-key tiles per row)   7 t_plain (tiles that end at or before S - window)
+ *   8 LDS bytes of pass 1   9 of pass 2   10 pass 1 asked for the > 64 KB LDS opt-in   11 pass 2 did
+ *   12..15 workgroups of pass 1 by the path they took: frozen reference point / frozen and repeated with the tracked maximum
+ *   after an overflow / tracked from the start (a row's first 16 logits span more than 40) / short prompt (t_plain == 0).
+ * The record reads the workspace of that call: ask before the workspace is reused or freed. */
+PKV_API int pkv_debug_h2o_route(int32_t* out, int n);
+/* ... and its per-row results (host pointers): wg_route[n_wg] receives the path code of every pass-1 workgroup (1 frozen,
+ * 2 repeat, 3 wide, 4 short; slot bh * grid.x + blockIdx.x, n_wg <= words 2 * 3 above), c_row[n_rows] the pass-1 output
+ * c_row = -log2 sum_j exp(x_ij) of every query row ([B*H][S], n_rows <= B*H*S).  PKV_ERR_SHAPE for more than was recorded. */
+PKV_API int pkv_debug_h2o_rows(int32_t* wg_route, int64_t n_wg, float* c_row, int64_t n_rows);
 /* Test hooks of the RELEASE library (tests/test_gpu_parity.py): two element-wise kernels that expose device functions the
  * hot kernels inline - the accurate exp() of finalize_kernel and the fp32 -> dtype rounding of every rounding point - so
  * that the suite checks the shipped code, not a copy.  Nothing on the product path launches them (~2 KB of code). */

@@ -112,6 +112,8 @@ def _load():
         "pkv_debug_wg_trace": (C.c_int, [vp]),
         "pkv_debug_score_route": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
         "pkv_debug_merge_route": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+        "pkv_debug_h2o_route": (C.c_int, [C.POINTER(C.c_int32), C.c_int]),
+        "pkv_debug_h2o_rows": (C.c_int, [C.POINTER(C.c_int32), i64, C.POINTER(C.c_float), i64]),
         "pkv_debug_exp": (C.c_int, [vp, vp, i64, vp]),
         "pkv_debug_unit_div": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, i64, vp]),
         "pkv_debug_round": (C.c_int, [i32, vp, vp, i64, vp]),

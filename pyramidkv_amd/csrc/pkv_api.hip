@@ -15,6 +15,7 @@
 namespace pkv { thread_local KernelEvents* g_kev = nullptr; unsigned g_dyn_lds_epoch = 1; }
 #ifdef PKV_DEBUG
 namespace pkv { int g_score_route[SR_WORDS]; int g_merge_route[MR_WORDS]; const unsigned int* g_merge_flags = nullptr; }
+namespace pkv { int g_h2o_route[H2R_WORDS]; const float* g_h2o_rowstat = nullptr; long long g_h2o_rows = 0, g_h2o_wgs = 0; }
 #endif
 using namespace pkv;
 
@@ -1022,12 +1023,36 @@ int pkv_debug_merge_route(int32_t* out, int n) {
   for (int i = 0; i < n && i < MR_WORDS; ++i) out[i] = g_merge_route[i];
   return PKV_OK;
 }
+// the codes of the last 16-bit H2O call sit behind its c_row (pkv_kernels.hpp); both stay valid until that workspace is reused
+static int h2o_fetch(int32_t* wg_route, int64_t n_wg, float* c_row, int64_t n_rows) {
+  if ((n_wg > 0 && !wg_route) || (n_rows > 0 && !c_row)) return PKV_ERR_NULL;
+  if (n_wg < 0 || n_rows < 0 || n_wg > g_h2o_wgs || n_rows > g_h2o_rows || !g_h2o_rowstat) return PKV_ERR_SHAPE;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && n_rows > 0) e = hipMemcpy(c_row, g_h2o_rowstat, (size_t)n_rows * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && n_wg > 0) e = hipMemcpy(wg_route, g_h2o_rowstat + g_h2o_rows, (size_t)n_wg * 4, hipMemcpyDeviceToHost);
+  return hip_rc(e);
+}
+int pkv_debug_h2o_rows(int32_t* wg_route, int64_t n_wg, float* c_row, int64_t n_rows) { return h2o_fetch(wg_route, n_wg, c_row, n_rows); }
+int pkv_debug_h2o_route(int32_t* out, int n) {
+  if (!out) return PKV_ERR_NULL;
+  if (g_h2o_rowstat) {
+    std::vector<int32_t> codes((size_t)g_h2o_wgs);
+    if (int rc = h2o_fetch(codes.data(), g_h2o_wgs, nullptr, 0)) return rc;
+    for (int w = H2R_N_FROZEN; w <= H2R_N_SHORT; ++w) g_h2o_route[w] = 0;
+    for (int32_t c : codes)
+      if (c >= H2O_WG_FROZEN && c <= H2O_WG_SHORT) ++g_h2o_route[H2R_N_FROZEN + c - H2O_WG_FROZEN];
+  }
+  for (int i = 0; i < n && i < H2R_WORDS; ++i) out[i] = g_h2o_route[i];
+  return PKV_OK;
+}
 #else   // release library: the trace hooks do not exist in the kernels (see pkv_kernels.hpp)
 int pkv_debug_topk_trace(void* device_u64x8) { return device_u64x8 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_wg_trace(void* device_u64) { return device_u64 ? PKV_ERR_UNSUPPORTED : PKV_OK; }
 int pkv_debug_build(void) { return 0; }
 int pkv_debug_score_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
 int pkv_debug_merge_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
+int pkv_debug_h2o_route(int32_t*, int) { return PKV_ERR_UNSUPPORTED; }
+int pkv_debug_h2o_rows(int32_t*, int64_t, float*, int64_t) { return PKV_ERR_UNSUPPORTED; }
 #endif
 
 int pkv_runtime_reset(void) {

@@ -46,6 +46,9 @@
 // pinned MFMAs, 32x32x16 MFMAs with an explicit software pipeline, the scale by 1/sqrt(D) on the matrix pipe, forced
 // occupancy, tile loads without a memory stream (the loop is not memory bound).
 #include <type_traits>
+#ifdef PKV_DEBUG
+#include <string.h>
+#endif
 #include "pkv_common.hpp"
 #include "pkv_kernels.hpp"
 
@@ -331,13 +334,16 @@ __global__ __launch_bounds__(256) void h2o_stats_kernel(H2OParams p) {
     tile_body(0, std::false_type{}, std::true_type{});
     for (int t = 1; t < t_plain; ++t) tile_body(t, std::false_type{}, std::false_type{});
     for (int t = t_plain > 1 ? t_plain : 1; t < ntiles; ++t) tile_body(t, std::true_type{}, std::false_type{});
-    if (!finish(true)) return;
+    if (!finish(true)) { PKV_H2O_WG(p, bh, tid, H2O_WG_FROZEN); return; }
     // a frozen row overflowed after all: repeat with the exact online maximum, tile 0 staged again
+    PKV_H2O_WG(p, bh, tid, H2O_WG_REPEAT);
     stage_load<KS>(stg, ks, 0);
     stage_store<KS>(stg, tiles[0], tid);
     __syncthreads();
 #pragma unroll
     for (int n = 0; n < 4; ++n) { m[n] = -INFINITY; mL[n] = 0.f; Z[n] = 0.f; }
+  } else {
+    PKV_H2O_WG(p, bh, tid, t_plain == 0 ? H2O_WG_SHORT : H2O_WG_WIDE);
   }
   for (int t = 0; t < t_plain; ++t) tile_body(t, std::false_type{}, std::true_type{});
   for (int t = t_plain; t < ntiles; ++t) tile_body(t, std::true_type{}, std::true_type{});
@@ -434,9 +440,16 @@ static bool strides_ok(const H2OParams& p) {
 hipError_t launch_h2o_stats(int dtype, const H2OParams& p, hipStream_t st) {
   if (!strides_ok(p)) return hipErrorInvalidValue;
   dim3 grid((p.S + HWG - 1) / HWG, p.B * p.H);
+#ifdef PKV_DEBUG
+  memset(g_h2o_route, 0, sizeof(g_h2o_route));
+  g_h2o_rowstat = p.rowstat; g_h2o_rows = (long long)p.B * p.H * p.S; g_h2o_wgs = (long long)grid.x * grid.y;
+  PKV_H2O_ROUTE(H2R_DTYPE, dtype); PKV_H2O_ROUTE(H2R_STATS_GRID_X, grid.x); PKV_H2O_ROUTE(H2R_STATS_GRID_Y, grid.y);
+  PKV_H2O_ROUTE(H2R_NTILES, (p.S + HT - 1) / HT); PKV_H2O_ROUTE(H2R_T_PLAIN, (p.S - p.w) / HT);   // as the kernel computes them
+#endif
 #define PKV_H2O_S(TT, KS)                                                                                             \
   do {                                                                                                                \
     const size_t lds_ = (size_t)2 * HT * 4 * KS * 16;                                                                 \
+    PKV_H2O_ROUTE(H2R_KS, KS); PKV_H2O_ROUTE(H2R_STATS_LDS, lds_); PKV_H2O_ROUTE(H2R_STATS_DYN_LDS, lds_ >= 64 * 1024);  \
     if (lds_ >= 64 * 1024) {                                                                                          \
       hipError_t e_ = dyn_lds(reinterpret_cast<const void*>(h2o_stats_kernel<TT, KS>), lds_);                    \
       if (e_ != hipSuccess) return e_;                                                                                \
@@ -453,9 +466,11 @@ hipError_t launch_h2o_colsum(int dtype, const H2OParams& p, hipStream_t st) {
   if (!strides_ok(p)) return hipErrorInvalidValue;
   const int L = p.S - p.w;
   dim3 grid((L + HWG - 1) / HWG, p.B * p.H);
+  PKV_H2O_ROUTE(H2R_COLSUM_GRID_X, grid.x); PKV_H2O_ROUTE(H2R_COLSUM_GRID_Y, grid.y);
 #define PKV_H2O_C(TT, KS)                                                                                             \
   do {                                                                                                                \
     const size_t lds_ = (size_t)2 * HT * 4 * KS * 16 + 2 * HT * 4;                                                    \
+    PKV_H2O_ROUTE(H2R_COLSUM_LDS, lds_); PKV_H2O_ROUTE(H2R_COLSUM_DYN_LDS, lds_ >= 64 * 1024);                        \
     if (lds_ >= 64 * 1024) {                                                                                          \
       hipError_t e_ = dyn_lds(reinterpret_cast<const void*>(h2o_colsum_kernel<TT, KS>), lds_);                    \
       if (e_ != hipSuccess) return e_;                                                                                \

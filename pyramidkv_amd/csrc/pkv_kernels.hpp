@@ -110,6 +110,37 @@ extern const unsigned int* g_merge_flags;      // device address of the flags wo
 #define PKV_MERGE_FLAG(p, bit) ((void)0)
 #endif
 
+// Route of the last 16-bit H2O score call (pkv_debug_h2o_route / pkv_debug_h2o_rows, debug build): launch_h2o_stats and
+// launch_h2o_colsum write the host's choices; every workgroup of h2o_stats_kernel of the debug build stores the code of the path
+// it took (enum H2OWgRoute) as one int32 at slot (bh, blockIdx.x) of the spare half of the rowstat slot - the workspace sizes that
+// slot for the fp32 form's float2 per row, the 16-bit kernels use B*H*S floats of it, and the codes start right behind them (the
+// workspace layout is the release one).  The last four words are counted from those codes.  launch_h2o_f32 records nothing.
+// Word order: include/pkv.h.
+enum H2ORouteWord {
+  H2R_DTYPE, H2R_KS, H2R_STATS_GRID_X, H2R_STATS_GRID_Y, H2R_COLSUM_GRID_X, H2R_COLSUM_GRID_Y, H2R_NTILES, H2R_T_PLAIN,
+  H2R_STATS_LDS, H2R_COLSUM_LDS, H2R_STATS_DYN_LDS, H2R_COLSUM_DYN_LDS, H2R_N_FROZEN, H2R_N_REPEAT, H2R_N_WIDE, H2R_N_SHORT, H2R_WORDS
+};
+enum H2OWgRoute : int {
+  H2O_WG_FROZEN = 1,             // frozen reference point, no row overflowed
+  H2O_WG_REPEAT = 2,             // frozen, a row overflowed: the row range ran again with the tracked maximum
+  H2O_WG_WIDE = 3,               // the look at the first 16 keys found a wide row: tracked maximum from the start
+  H2O_WG_SHORT = 4,              // t_plain == 0: tracked maximum, every tile through the edge body
+};
+#ifdef PKV_DEBUG
+extern int g_h2o_route[H2R_WORDS];
+extern const float* g_h2o_rowstat;             // device address of c_row [B*H][S] of the last 16-bit H2O call; the codes follow it
+extern long long g_h2o_rows, g_h2o_wgs;        // B*H*S and B*H*grid.x of that call
+#define PKV_H2O_ROUTE(i, v) (pkv::g_h2o_route[(i)] = (int)(v))
+#define PKV_H2O_WG(p, bh, tid, code)                                                                                \
+  do {                                                                                                              \
+    if ((tid) == 0)                                                                                                 \
+      reinterpret_cast<int*>((p).rowstat + (int64_t)(p).B * (p).H * (p).S)[(int64_t)(bh) * gridDim.x + blockIdx.x] = (code); \
+  } while (0)
+#else
+#define PKV_H2O_ROUTE(i, v) ((void)0)
+#define PKV_H2O_WG(p, bh, tid, code) ((void)0)
+#endif
+
 struct LogitsParams {
   unsigned long long* wgtrace = nullptr; // debug: per-workgroup (start,end) wall clock, may be null
   const void* q = nullptr;

@@ -389,32 +389,25 @@ def test_h2o_scores_key_norm_outliers(P, dt):
     """Pass 1 of the H2O kernels takes its exponentials relative to a FROZEN reference point (the lane's maximum over the
     first key tile) unless a look at the first 16 keys says the rows are wide (span > 40: tracked maximum from the start,
     round 6), and repeats a workgroup with the tracked maximum when a frozen row overflows after all (pkv_h2o.hip).
-    Keys with a huge norm in a direction no query looks at; an outlier that only the queries of one workgroup look at (both
-    paths in one launch); very large logits (tracked from the start); rows just wide enough to be tracked (std ~ 20: the
-    round-5 form froze them and repeated most workgroups - the advisor's finding)."""
+    What the four inputs (tests/h2o_routes.py: legacy_outlier_inputs) exercise, by the debug library's route record and its
+    CPU restatement (tests/test_h2o_routes_plan.py::test_legacy_outlier_cases_take_the_stated_routes):
+      outlier_keys_no_row_looks_at  keys with a huge norm in a direction no query looks at (q[..., 0] = 0: they score exactly
+                                    0): every workgroup stays FROZEN, the largest per-lane ln Z is 6.1;
+      outlier_in_the_look_of_wg0    an outlier key (7, inside the 16-key look) that only the queries of the first workgroup look
+                                    at: workgroup 0 is WIDE (span 398), workgroups 1-4 are frozen - two paths in one launch;
+      large_logits                  very large logits: every workgroup WIDE (tracked from the start);
+      wide_rows_tracked             rows just wide enough to be tracked (std ~ 20: the round-5 form froze them and repeated
+                                    most workgroups - the advisor's finding): every workgroup WIDE.
+    None of them reaches the REPEAT path (the first two were built for round 4's norm bound and named *_repeat until the record
+    showed otherwise); tests/test_gpu_h2o_routes.py does, with planted keys outside the look."""
+    from h2o_routes import LEGACY_NAMES, legacy_outlier_inputs
     S, w, D = 1200, 8, 128
-    for case in ("all_rows_repeat", "some_rows_repeat", "large_logits", "wide_rows_tracked"):
-        # large logits on the lattice: every q.k is an exact multiple of 16 below 2^15 (no accumulation-order rounding of the
-        # model-dtype logits, whose unit is up to 4 there - one flipped logit moves a probability by several per cent)
-        q, k, _ = make_qkv(1, 2, S, D, dt, "lattice" if case in ("large_logits", "wide_rows_tracked") else "gauss", 97)
-        if case == "all_rows_repeat":
-            q[..., 0] = 0
-            k[:, :, 5::300, :] = 0
-            k[:, :, 5::300, 0] = 3000.0 if dt == "bf16" else 2000.0           # bound ~ 11 * 3000 / 11.3 = 2900
-        elif case == "some_rows_repeat":
-            q[:, :, :256, :] *= 0.01                                          # first workgroup: queries along the outlier key,
-            q[:, :, :256, 0] = 3.0                                            # row maximum = bound / 1.02: inside the window
-            q[:, :, 256:, 0] = 0                                              # all other rows: ~400 below their bound
-            k[:, :, 7, :] = 0
-            k[:, :, 7, 0] = 1500.0
-        elif case == "large_logits":
-            q *= 16
-            k *= 16                                                           # logits ~ N(0, 106^2): row maxima ~ 350
-        else:
-            q *= 8
-            k *= 8                                                            # logits ~ N(0, 27^2): a 16-key sample spans ~90, row maxima ~ +70 above it
-            # (tools/probes/h2o_wide_case.py, x5 .. x10: the tracked and the frozen form differ from the oracle in the same 0-10 of
-            # 2384 scores by one unit; at x7 in fp16 one of the tracked form's three sits two units away - two flipped roundings)
+    assert LEGACY_NAMES == ["outlier_keys_no_row_looks_at", "outlier_in_the_look_of_wg0", "large_logits", "wide_rows_tracked"]
+    for case in LEGACY_NAMES:
+        q, k = legacy_outlier_inputs(case, dt)
+        assert q.shape == (1, 2, S, D)
+        # (tools/probes/h2o_wide_case.py, x5 .. x10: the tracked and the frozen form differ from the oracle in the same 0-10 of
+        # 2384 scores by one unit; at x7 in fp16 one of the tracked form's three sits two units away - two flipped roundings)
         want = O.h2o_scores(q, k, w)
         got = P.ops.score_h2o(q.to(DEV), k.to(DEV), w).cpu()
         assert torch.isfinite(got.float()).all(), case
