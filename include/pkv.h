@@ -28,6 +28,7 @@ extern "C" {
 
 #define PKV_VERSION 204 /* still 0.2.4: + pkv_debug_h2o_route, pkv_debug_h2o_rows (two debug hooks added within 0.2.4: no struct layout
                            change, no workspace change; the release library answers PKV_ERR_UNSUPPORTED).
+                           + pkv_decode_attn_think (one more symbol added within 0.2.4 on the same terms as the three below).
                            + pkv_decode_attn_splits, pkv_decode_attn_workspace_bytes, pkv_decode_attn_flat (three more symbols
                            added within 0.2.4, exactly as the ThinK ones below: no struct layout change, no profiling class, PKV_K_COUNT
                            stays 9; a host that needs them checks for the symbols).
@@ -63,7 +64,7 @@ enum pkv_status {
 
 /* PKV_F32: pkv_score_window, pkv_score_h2o, pkv_topk(_ws), pkv_gather_compact, pkv_gather_streaming, pkv_gather_flat,
  * pkv_compress, pkv_compress_h2o, pkv_compress_l2norm, pkv_think_prune, pkv_select, pkv_merge_compact, pkv_ada_budget_rows, pkv_ada_metadata and
- * pkv_update_flatten_view and pkv_decode_attn_flat, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
+ * pkv_update_flatten_view, pkv_decode_attn_flat and pkv_decode_attn_think, D in {64,128,256} (256 since 0.2.0), topk <= 4096; every other entry point (pkv_sort_rows, pkv_ada_budget,
  * pkv_ada_budget_topm, pkv_ada_adaptive_lists, pkv_ada_select) answers PKV_ERR_DTYPE / PKV_ERR_UNSUPPORTED. */
 enum pkv_dtype { PKV_BF16 = 0, PKV_F16 = 1, PKV_F32 = 2 };
 enum pkv_pool { PKV_POOL_NONE = 0, PKV_POOL_AVG = 1, PKV_POOL_MAX = 2 };
@@ -361,6 +362,45 @@ PKV_API int pkv_decode_attn_flat(int32_t dtype, int32_t H, int32_t head_dim, con
                                  int32_t max_seqlen_k /* launch hint, >= 1 */, float scale, int32_t splits /* 0 = default */,
                                  void* out /* dtype [H][head_dim] contiguous */, float* lse_out /* [H], may be NULL */,
                                  void* ws, size_t ws_bytes, pkv_stream_t stream);
+
+/* The same decode step over the ThinK cache (llama_model_think.py:175-195; the cache update_think and pkv_think_prune leave):
+ * per head n_pruned keys that keep `kept` = Dk of their head_dim channels, then n_full full-width keys, and n_pruned + n_full
+ * values.  With c_0 < c_1 < ... the channels of head h with keep[h][c] != 0, ascending:
+ *   s_j = fp32(sum_{p < kept} q[h,c_p] * k_pruned[h,j,p]) * scale          j < n_pruned
+ *   s_j = fp32(sum_{d < head_dim} q[h,d] * k_full[h,j - n_pruned,d]) * scale   j >= n_pruned
+ *   out[h] = dtype(sum_j softmax_fp32(s)_j * v[h,j]),  lse[h]
+ * with the rounding points of the flat-cache call above (products and sums of the inputs as they are, the accurate exp, ONE
+ * correctly rounded fp32 division, ONE round-to-nearest-even to dtype, the logarithm of lse in fp64) and the sum of a score's
+ * products taken in fp64 and rounded to fp32 ONCE before the multiplication by scale: s_j is the correctly rounded fp32 dot
+ * product times scale.  n_pruned + n_full = 0 gives zeros and lse = -inf.  The mask is device data and not checked: the first `kept` set channels of a head are used, a
+ * head with fewer meets the missing ones as a zero query, and no mask content makes the library read out of range.
+ * Chunks of PKV_DECODE_CHUNK rows: first ceil(n_pruned / chunk) of pruned rows, then ceil(n_full / chunk) of full-width rows (a
+ * chunk never straddles the two parts); chunk c belongs to split c % splits, the grid is (H, splits), splits > 1 adds the
+ * combine launch over the same partials.  The order of every fp32 sum is a function of (head_dim, kept, dtype, splits) and
+ * PKV_DECODE_CHUNK alone: two calls give the same bits.
+ *   q:        dtype [H] rows of head_dim elements, q_stride ELEMENTS between heads
+ *   keep:     uint8 [H][head_dim] contiguous, non-zero = kept (a torch bool mask as it is)
+ *   k_pruned: dtype [H][n_pruned][kept] contiguous.  A row is kept * e bytes, so rows and head bases are not 16-byte aligned in
+ *             general; the library fetches the 16-byte blocks that enclose the bytes it needs.  The base must be 16-byte
+ *             aligned and the ALLOCATION must extend to the next 16-byte multiple behind the last element (every device
+ *             allocator's granularity does that); what lies in those bytes does not matter.  May be NULL when n_pruned == 0.
+ *   k_full:   dtype [H] heads of [n_full][head_dim] rows, k_full_stride ELEMENTS between heads; may be NULL when n_full == 0
+ *   v:        dtype [H] heads of [n_pruned + n_full][head_dim] rows, v_stride ELEMENTS between heads
+ *   splits:   0 = the flat-cache default for H heads of n_pruned + n_full rows (at least 1), else 1 .. PKV_DECODE_MAX_SPLITS
+ *   out, lse_out, ws: as above; the workspace size is the flat-cache one for the same (H, head_dim, splits)
+ * Nothing outside out, lse_out and ws is written.
+ * PKV_ERR_DTYPE: dtype; PKV_ERR_SHAPE: H < 1, head_dim not in {64,128,256}, kept not in 1 .. head_dim, n_pruned < 0, n_full < 0,
+ * a stride shorter than its rows, splits out of range, a scale that is not finite; PKV_ERR_NULL; PKV_ERR_ALIGN: q, k_full, v,
+ * out, ws or one of the three strides breaks 16-byte rows, or k_pruned is not 16-byte aligned; PKV_ERR_WORKSPACE.  In that
+ * order, all before any HIP call. */
+PKV_API int pkv_decode_attn_think(int32_t dtype, int32_t H, int32_t head_dim, int32_t kept /* Dk */,
+                                  const void* q, int64_t q_stride /* elements between heads */,
+                                  const uint8_t* keep /* [H][head_dim], non-zero = kept: the cache's bool mask as it is */,
+                                  const void* k_pruned /* dtype [H][n_pruned][kept] contiguous */, int32_t n_pruned,
+                                  const void* k_full, int64_t k_full_stride /* elements between heads */, int32_t n_full,
+                                  const void* v, int64_t v_stride /* dtype [H][n_pruned + n_full][head_dim], elements between heads */,
+                                  float scale, int32_t splits /* 0 = default */, void* out, float* lse_out /* may be NULL */,
+                                  void* ws, size_t ws_bytes, pkv_stream_t stream);
 
 /* ---- multi-GPU: the one exchange step of the head-sharded path (the reference has no
  * collective: run_longbench.py:390 only places layers with device_map="auto") ----

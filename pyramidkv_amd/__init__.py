@@ -1,5 +1,7 @@
 """pyramidkv_amd - MI355X (gfx950) native prefill-time KV-cache eviction (PyramidKV / SnapKV / H2O /
-StreamingLLM / Ada-SnapKV / HeadKV / L2Norm ``update_kv``, ThinK ``update_think``), behind the reference's own plugin surface.
+StreamingLLM / Ada-SnapKV / HeadKV / L2Norm ``update_kv``, ThinK ``update_think``) and the decode-time attention over the caches
+the model's own attention cannot read (``ops.decode_attn_flat``: the flat Ada-SnapKV / HeadKV cache; ``ops.decode_attn_think``: the
+channel-pruned ThinK cache), behind the reference's own plugin surface.
 
 Importing this package loads ``libpkv.so`` (hand-written HIP kernels behind a C ABI, include/pkv.h)
 and fails loudly if it has not been built.

@@ -30,6 +30,7 @@ THINK_QROWS = 32
 # decode attention over the flat cache (include/pkv.h, same names): rows per chunk - chunk c of a head belongs to split c % splits
 PKV_DECODE_CHUNK = 128
 PKV_DECODE_MAX_SPLITS = 64
+DECODE_TILE_BYTES = 16384    # csrc/pkv_kernels.hpp: pruned-key bytes the ThinK decode kernel stages in LDS at a time
 
 PKV_VERSION = 204            # include/pkv.h PKV_VERSION this binding was written against (checked when the library loads)
 
@@ -105,6 +106,8 @@ def _load():
         "pkv_decode_attn_splits": (C.c_int, [i32, i32, i32]),
         "pkv_decode_attn_workspace_bytes": (sz, [i32, i32, i32]),
         "pkv_decode_attn_flat": (C.c_int, [i32, i32, i32, vp, i64, vp, vp, vp, i32, C.c_float, i32, vp, vp, vp, sz, vp]),
+        "pkv_decode_attn_think": (C.c_int, [i32, i32, i32, i32, vp, i64, vp, vp, i32, vp, i64, i32, vp, i64, C.c_float, i32, vp, vp, vp, sz,
+                                            vp]),
         "pkv_allgather_indices": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, sz, vp]),
         "pkv_last_nccl_error": (C.c_int, []),
         "pkv_debug_build": (C.c_int, []),

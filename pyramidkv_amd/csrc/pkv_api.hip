@@ -1001,6 +1001,39 @@ int pkv_decode_attn_flat(int32_t dtype, int32_t H, int32_t head_dim, const void*
   return hip_rc(launch_decode_attn(dtype, p, static_cast<hipStream_t>(stream)));
 }
 
+// ---- the same step over the ThinK cache (llama_model_think.py:175-195): pruned keys of `kept` channels, then full-width keys ----
+int pkv_decode_attn_think(int32_t dtype, int32_t H, int32_t head_dim, int32_t kept, const void* q, int64_t q_stride, const uint8_t* keep,
+                          const void* k_pruned, int32_t n_pruned, const void* k_full, int64_t k_full_stride, int32_t n_full, const void* v,
+                          int64_t v_stride, float scale, int32_t splits, void* out, float* lse_out, void* ws, size_t ws_bytes,
+                          pkv_stream_t stream) {
+  if (dtype != PKV_BF16 && dtype != PKV_F16 && dtype != PKV_F32) return PKV_ERR_DTYPE;
+  if (H < 1 || (head_dim != 64 && head_dim != 128 && head_dim != 256) || kept < 1 || kept > head_dim || n_pruned < 0 || n_full < 0)
+    return PKV_ERR_SHAPE;
+  const int64_t n = (int64_t)n_pruned + n_full;
+  if (q_stride < head_dim || k_full_stride < (int64_t)n_full * head_dim || v_stride < n * head_dim) return PKV_ERR_SHAPE;
+  if (splits < 0 || splits > PKV_DECODE_MAX_SPLITS || !std::isfinite(scale)) return PKV_ERR_SHAPE;
+  if (!q || !keep || !v || !out || (n_pruned > 0 && !k_pruned) || (n_full > 0 && !k_full)) return PKV_ERR_NULL;
+  // the default of the flat cache for a head of n rows: never more than ceil(n / chunk) <= pruned chunks + full-width chunks
+  if (splits == 0) splits = std::max(1, decode_splits(H, head_dim, (int)std::min<int64_t>(n, INT32_MAX)));
+  if (splits > 1 && !ws) return PKV_ERR_NULL;
+  const int64_t row_mask = dtype == PKV_F32 ? 3 : 7;     // elements of a 16-byte piece - 1
+  if (misaligned(q) || misaligned(v) || misaligned(out) || (n_full > 0 && misaligned(k_full)) || (n_pruned > 0 && misaligned(k_pruned)) ||
+      (q_stride & row_mask) || (k_full_stride & row_mask) || (v_stride & row_mask) || (reinterpret_cast<uintptr_t>(lse_out) & 3) ||
+      (splits > 1 && misaligned(ws)))
+    return PKV_ERR_ALIGN;
+  DecodeParams p;
+  if (splits > 1) {
+    const DecodeWs W = decode_ws(H, head_dim, splits);
+    if (ws_bytes < W.total) return PKV_ERR_WORKSPACE;
+    p.part_ml = reinterpret_cast<float*>(static_cast<char*>(ws) + W.off_ml);
+    p.part_acc = reinterpret_cast<float*>(static_cast<char*>(ws) + W.off_acc);
+  }
+  p.q = q; p.k = k_full; p.v = v; p.keep = keep; p.k_pruned = k_pruned; p.out = out; p.lse = lse_out;   // cu_klen stays null
+  p.H = H; p.D = head_dim; p.splits = splits; p.q_stride = q_stride; p.scale = scale;
+  p.kept = kept; p.n_pruned = n_pruned; p.n_full = n_full; p.k_stride = k_full_stride; p.v_stride = v_stride;
+  return hip_rc(launch_decode_attn(dtype, p, static_cast<hipStream_t>(stream)));
+}
+
 /* ---- debug / test hooks (not part of the drop-in surface) ---- */
 #ifdef PKV_DEBUG
 int pkv_debug_topk_trace(void* device_u64x8) { g_topk_trace = static_cast<unsigned long long*>(device_u64x8); return PKV_OK; }

@@ -328,13 +328,18 @@ struct ThinkParams {
   int64_t qs_b = 0, qs_h = 0, qs_s = 0;
 };
 
-// Single-query attention over the flat var-len cache (pkv_decode.hip).  The chunk length PKV_DECODE_CHUNK (include/pkv.h) and
-// `splits` fix the order of every fp32 sum.
+// Single-query attention over the flat var-len cache, or over the ThinK cache (pkv_decode.hip).  The chunk length
+// PKV_DECODE_CHUNK (include/pkv.h) and `splits` fix the order of every fp32 sum; for the ThinK kernel `kept` as well.
+constexpr int DECODE_TILE_BYTES = 16384;  // pruned-key bytes decode_think_kernel stages in LDS at a time (whole rows of kept * e bytes)
 struct DecodeParams {
   const void* q = nullptr;    // [H][q_stride] model dtype, head_dim elements used
-  const void* k = nullptr;    // [sum_h n_h][D] contiguous
-  const void* v = nullptr;
-  const int32_t* cu_klen = nullptr; // [H+1]
+  const void* k = nullptr;    // flat: [sum_h n_h][D] contiguous.  ThinK: the full-width keys, [H] heads of n_full rows, k_stride apart
+  const void* v = nullptr;    // flat: as k.  ThinK: [H] heads of n_pruned + n_full rows, v_stride apart
+  const int32_t* cu_klen = nullptr; // flat: [H+1].  ThinK: null - that is how the launcher and the combine kernel tell the two apart
+  const uint8_t* keep = nullptr;    // ThinK: [H][D], non-zero = kept channel
+  const void* k_pruned = nullptr;   // ThinK: [H][n_pruned][kept] contiguous, 16-byte aligned base
+  int kept = 0, n_pruned = 0, n_full = 0;
+  int64_t k_stride = 0, v_stride = 0;   // ThinK: elements between heads
   void* out = nullptr;        // [H][D] model dtype
   float* lse = nullptr;       // [H] or null
   float* part_ml = nullptr;   // splits > 1: [H][splits][2] (max, sum) of every (head, split) that holds a chunk
@@ -391,7 +396,7 @@ hipError_t launch_l2norm(int dtype, const L2NormParams& p, hipStream_t st);
 // dst [BH][n] = src row bh / G (stride src_stride), entries 0..n-1
 hipError_t launch_idx_expand(const int32_t* src, int64_t src_stride, int32_t* dst, int BH, int n, int G, hipStream_t st);
 hipError_t launch_think(int dtype, const ThinkParams& p, hipStream_t st);      // scan -> select -> compaction, three launches
-hipError_t launch_decode_attn(int dtype, const DecodeParams& p, hipStream_t st);   // one launch; splits > 1: + the combine launch
+hipError_t launch_decode_attn(int dtype, const DecodeParams& p, hipStream_t st);   // one launch; splits > 1: + the combine launch; cu_klen == null: the ThinK kernel
 hipError_t launch_debug_sqrt(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_exp(const float* in, float* out, int64_t n, hipStream_t st);
 hipError_t launch_debug_round(int dtype, const float* in, uint16_t* out, int64_t n, hipStream_t st);

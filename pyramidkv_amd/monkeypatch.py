@@ -18,7 +18,8 @@ As in the reference the cache stores all H (query) heads, because K/V are expand
 appends through ``pkv_update_flatten_view`` and attends per head over its own rows - the reference calls
 ``flash_attn_varlen_func`` there, this adapter calls ``ops.decode_attn_flat`` (``pkv_decode_attn_flat``) on HIP tensors; the
 padded-batch softmax in plain PyTorch ops below, ``varlen_decode_attention``, serves CPU tensors (the plumbing tests).  ``think`` (reference llama_model_think.py) keeps pruned keys next to full-width recent
-ones: pass a ``pyramidkv_amd.ThinKCache()`` (batch 1); its decode step is plain PyTorch as well.
+ones: pass a ``pyramidkv_amd.ThinKCache()`` (batch 1); its decode step calls ``ops.decode_attn_think`` (``pkv_decode_attn_think``) on
+HIP tensors, and ``think_decode_attention``, the same step in plain PyTorch ops, serves CPU tensors.
 """
 from __future__ import annotations
 
@@ -45,8 +46,9 @@ _THINK_METHODS: Dict[str, str] = {"think": "init_think_native"}
 _cluster_module = _utils
 # hand K/V to update_kv BEFORE repeat_kv when the cluster accepts it (pyramidkv_amd's do); False = the reference's order
 skip_repeat_kv = True
-# the flat-cache decode step on HIP tensors: ops.decode_attn_flat (the native kernel); False = varlen_decode_attention, the eager
-# statement of the same attention (what CPU tensors always take)
+# the decode step of the flat cache and of the ThinK cache on HIP tensors: ops.decode_attn_flat / ops.decode_attn_think (the native
+# kernels); False = varlen_decode_attention / think_decode_attention, the eager statements of the same attention (what CPU
+# tensors always take)
 native_decode_attention = True
 
 
@@ -171,7 +173,8 @@ def _make_forward(method: str, apply_rotary_pos_emb: Callable):
 
 def _make_think_forward(apply_rotary_pos_emb: Callable):
     """ThinK (reference llama_model_think.py:87-216): prefill calls ``kv_cluster.update_think`` into a
-    ``pyramidkv_amd.ThinKCache``; a decode step scores the pruned keys with the query's kept channels only."""
+    ``pyramidkv_amd.ThinKCache``; a decode step scores the pruned keys with the query's kept channels only - on HIP tensors
+    in ``ops.decode_attn_think``, one native call per layer, otherwise in ``think_decode_attention``."""
     init_name = _THINK_METHODS["think"]
 
     def forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None, **kwargs):
@@ -208,15 +211,26 @@ def _make_think_forward(apply_rotary_pos_emb: Callable):
             _track_tokens(past_key_values, self.layer_idx, 1, False)
             past_key_values._seen_tokens = past_key_values._pkv_seen_tokens
             kp = past_key_values.key_cache_pruned[self.layer_idx]
-            qp = q.gather(-1, past_key_values.keep_idx[self.layer_idx].unsqueeze(2))                # the query's kept channels (:177-178)
-            w = torch.cat([torch.matmul(qp, kp.transpose(2, 3)), torch.matmul(q, kr.transpose(2, 3))], dim=-1) * self.scaling
-            w = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)    # :193
-            attn = torch.matmul(w, vv).transpose(1, 2).contiguous()
+            if native_decode_attention and _is_hip(kr):
+                out = _ops.decode_attn_think(q[0, :, 0], past_key_values.mask[self.layer_idx][0], kp[0], kr[0], vv[0], self.scaling)
+                attn = out[None, None]                                    # [1, 1, H, D]
+            else:
+                attn = think_decode_attention(q, past_key_values.keep_idx[self.layer_idx], kp, kr, vv, self.scaling)
         attn = attn.reshape(*input_shape, -1).contiguous()
         return self.o_proj(attn), None
 
     forward.__name__ = "attn_forward_think"
     return forward
+
+
+def think_decode_attention(q, keep_idx, k_pruned, k_full, v, scaling):
+    """One query token over the ThinK cache (reference llama_model_think.py:175-195): q [1, H, 1, D], keep_idx int64
+    [1, H, Dk] (the kept channels, ascending), k_pruned [1, H, R, Dk], k_full [1, H, T, D], v [1, H, R + T, D].  The query's
+    kept channels score the pruned keys, the whole query the full-width ones; fp32 softmax over both.  -> [1, 1, H, D]."""
+    qp = q.gather(-1, keep_idx.unsqueeze(2))                              # the query's kept channels (:177-178)
+    w = torch.cat([torch.matmul(qp, k_pruned.transpose(2, 3)), torch.matmul(q, k_full.transpose(2, 3))], dim=-1) * scaling
+    w = F.softmax(w, dim=-1, dtype=torch.float32).to(q.dtype)             # :193
+    return torch.matmul(w, v).transpose(1, 2).contiguous()
 
 
 def varlen_decode_attention(q, k_flat, v_flat, cu_klen, max_seqlen_k, scaling):

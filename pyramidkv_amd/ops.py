@@ -757,3 +757,50 @@ def decode_attn_flat(q: torch.Tensor, k_flat: torch.Tensor, v_flat: torch.Tensor
         if rc:
             N.check(rc, "pkv_decode_attn_flat")
     return (out, lse) if return_lse else out
+
+
+def decode_attn_think(q: torch.Tensor, keep: torch.Tensor, k_pruned: torch.Tensor, k_full: torch.Tensor, v: torch.Tensor, scaling: float,
+                      splits: Optional[int] = None, return_lse: bool = False):
+    """One query row per head over the ThinK cache (llama_model_think.py:175-195), in one C call on the current stream: the
+    query's kept channels against the R pruned keys, the whole query against the T full-width keys, one fp32 softmax over the
+    R + T scores, the weighted values.  q: [H, D]; keep: bool or uint8 [H, D], non-zero = kept channel (used through a uint8
+    view, not copied); k_pruned: [H, R, Dk] holding the kept channels in ascending order; k_full: [H, T, D]; v: [H, R + T, D].
+    An unpruned layer is R = 0, Dk = D.  ``splits`` overrides the default split count (1 .. PKV_DECODE_MAX_SPLITS).
+    Returns out [H, D] in q's dtype, then lse float32 [H] with ``return_lse``.  R + T = 0 gives zeros, lse = -inf."""
+    _require_gpu(q, keep, k_pruned, k_full, v)
+    if keep.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"expected keep to be bool or uint8, got {keep.dtype}")
+    if q.dim() != 2 or keep.shape != q.shape or k_pruned.dim() != 3 or k_full.dim() != 3 or v.dim() != 3 or \
+            not (k_pruned.shape[0] == k_full.shape[0] == v.shape[0] == q.shape[0]) or k_full.shape[2] != q.shape[1] or \
+            v.shape[2] != q.shape[1] or not 1 <= k_pruned.shape[2] <= q.shape[1] or v.shape[1] != k_pruned.shape[1] + k_full.shape[1] or \
+            not (q.dtype == k_pruned.dtype == k_full.dtype == v.dtype):
+        raise ValueError(f"decode_attn_think: q {tuple(q.shape)} {q.dtype}, keep {tuple(keep.shape)}, k_pruned {tuple(k_pruned.shape)} "
+                         f"{k_pruned.dtype}, k_full {tuple(k_full.shape)} {k_full.dtype} and v {tuple(v.shape)} {v.dtype} do not belong together")
+    H, D = q.shape
+    R, Dk, T = k_pruned.shape[1], k_pruned.shape[2], k_full.shape[1]
+    code = N.dtype_code(q.dtype)
+    es = q.element_size()
+
+    def rows16(t):                                      # [H, n, D]: rows contiguous, head stride and base keep them 16-byte aligned
+        if t.stride(2) != 1 or t.stride(1) != D or (t.stride(0) * es) % 16 or t.stride(0) < t.shape[1] * D or t.data_ptr() % 16:
+            t = t.contiguous()
+        return t
+
+    if q.stride(1) != 1 or (q.stride(0) * es) % 16 or q.stride(0) < D or q.data_ptr() % 16:
+        q = q.contiguous()
+    k_full, v = rows16(k_full), rows16(v)
+    keep = keep.contiguous().view(torch.uint8)
+    if R and (not k_pruned.is_contiguous() or k_pruned.data_ptr() % 16):
+        k_pruned = k_pruned.contiguous()
+    sp = int(splits) if splits else max(N.lib.pkv_decode_attn_splits(H, D, R + T), 1)
+    v_ptr = v.data_ptr() if R + T else q.data_ptr()     # an empty tensor has no storage; without rows no V address is read
+    with _DeviceGuard(q.device):
+        ws, st = _workspace_and_stream(max(N.lib.pkv_decode_attn_workspace_bytes(H, D, sp), 1), q.device)
+        out = torch.empty(H, D, dtype=q.dtype, device=q.device)
+        lse = torch.empty(H, dtype=torch.float32, device=q.device) if return_lse else None
+        rc = N.lib.pkv_decode_attn_think(code, H, D, Dk, q.data_ptr(), q.stride(0), keep.data_ptr(), k_pruned.data_ptr() if R else None, R,
+                                         k_full.data_ptr() if T else None, k_full.stride(0), T, v_ptr, v.stride(0), float(scaling),
+                                         sp, out.data_ptr(), lse.data_ptr() if lse is not None else None, ws.data_ptr(), ws.numel(), st)
+        if rc:
+            N.check(rc, "pkv_decode_attn_think")
+    return (out, lse) if return_lse else out
